@@ -71,7 +71,28 @@ def parse():
     ap.add_argument("--native-option", action="append", default=[], help=argparse.SUPPRESS)          # developer: name=value, psdr_scene_set_option on the headline scene's handle (A/B runs)
     ap.add_argument("--hip-lib", default=None, help=argparse.SUPPRESS)          # developer: another build of libpsdr_hip.so (tools/build_variant_lib.sh)
     ap.add_argument("--no-c4-strong", action="store_true", help="skip the c4_strong block (BASELINE configs[3]: cbox_bunny 1024^2, global spp 512 sharded over the ranks)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one float32 .npy file per array.  An array larger than its even share of DUMP_LIMIT_BYTES is replaced by a sample of its
+    elements at fixed positions (seeded, sorted), so that two builds run with the same arguments can be compared file by file."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def stream_model_bytes(slots, rays, derivative):
@@ -552,12 +573,15 @@ def tree_scenes(args):
 
 
 def relaunch_under_torchrun(args):
-    """`python bench.py --gpus N` without a launcher: re-execute under torch.distributed.run, one process per GPU (what the driver's own
-    command line does for N > 1).  PSDR_BENCH_ONE_GPU=1 (developer switch) lets the N ranks share cuda:0 over gloo."""
+    """`python bench.py --gpus N` without a launcher: run this script under torch.distributed.run, one process per GPU (what the driver's own
+    command line does for N > 1), as a child process, and exit with its status.  This process never opens a GPU itself: the device count comes
+    from a short-lived child as well.  PSDR_BENCH_ONE_GPU=1 (developer switch) lets the N ranks share cuda:0 over gloo."""
     import socket
-    n_dev = torch.cuda.device_count()
-    if n_dev < args.gpus and os.environ.get("PSDR_BENCH_ONE_GPU") != "1":
-        raise SystemExit("bench.py --gpus %d: only %d GPU(s) visible" % (args.gpus, n_dev))
+    if os.environ.get("PSDR_BENCH_ONE_GPU") != "1":
+        r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True, text=True, check=True)
+        n_dev = int(r.stdout.split()[-1])
+        if n_dev < args.gpus:
+            raise SystemExit("bench.py --gpus %d: only %d GPU(s) visible" % (args.gpus, n_dev))
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
@@ -565,7 +589,7 @@ def relaunch_under_torchrun(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def rank_devices(dist, local_rank):
@@ -641,6 +665,8 @@ def run_c4(args, world, rank, local_rank, dist, devices, rccl):
         tt = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"renderC_image": out[0].numpy(), "grad_vertex_positions": out[1].numpy(), "grad_albedo": out[2].numpy()})
     value = 2.0 * res * res * spp * args.steps / dt / 1e6
     T = int(sc.tables(0)["num_tris"])
     # the wavefront stages' stream traffic against the HBM roofline: measured on one GPU's share of the 8-GPU job (64 spp: the launch size at
@@ -832,8 +858,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    # only the last step's outputs are kept (--dump-outputs): a renderD result still alive in the next step would be pushed through the renderer again
+    # by that step's enoki.forward, which serves every live renderD result
+    for _ in range(args.steps - 1):
         w.surface_step()
+    out = w.surface_step()
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -843,6 +872,9 @@ def main():
         tt = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"renderC_image": out[0].numpy(), "renderD_image": out[1].numpy(), "renderD_grad_albedo": out[2].numpy()})
+    del out
     local_slots = args.res * args.res * args.spp
     slots_per_pass = local_slots * world                             # whole job
     value = 2.0 * slots_per_pass * args.steps / dt / 1e6

@@ -91,7 +91,7 @@ def test_bench_c4_over_rccl_at_world_size_one():
 
 
 def test_bench_relaunches_itself_for_two_ranks():
-    """`python bench.py --gpus 2` WITHOUT a launcher on the command line: the script re-executes itself under torch.distributed.run (bench.py
+    """`python bench.py --gpus 2` WITHOUT a launcher on the command line: the script runs itself under torch.distributed.run as a child process (bench.py
     relaunch_under_torchrun); PSDR_BENCH_ONE_GPU=1 lets the two ranks share cuda:0 over gloo."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PSDR_BENCH_ONE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
