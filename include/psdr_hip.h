@@ -308,28 +308,43 @@ int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *opts,
    All pointers are device pointers; vertices [V][3], faces [T][3] int32 (global vertex ids), rows [T][row_stride >= 22] in the
    TriangleInfo layout (PSDR_TRI_STRIDE words when written straight into tri_info), edges [E][5] int32 = v0, v1, face0, face1
    (-1: boundary), opposite vertex of face0 (global ids; Mesh::m_edge_indices, mesh.cpp:154-196).  The *_rev entry points ADD the
-   adjoints into a_v / a_rows / a_w2s (the caller zeroes them). */
+   adjoints into a_v / a_rows / a_w2s (the caller zeroes them).  The *_jvp entry points are forward mode: they take the primal inputs and
+   ONE tangent per differentiable input (a null tangent = zero) and WRITE the tangent of the differentiable output, with the launches and
+   layouts of the primal entry.  The keep masks are primal-only: no tangent flows through them. */
 /* World positions (Mesh::configure, src/shape/mesh.cpp:226-232: transform_pos of include/psdr/core/transform.h:84-88 by the mesh's to_world):
    v_raw [V][3] object-space positions, vmesh [V] int32 = the mesh of every vertex, mats [M][16] row-major to_world matrices.
    The reverse entry point WRITES a_raw (adjoint of v_raw; the matrices carry no gradient on this path: the caller keeps the torch chain when they do). */
 int psdr_geo_world_vertices_fwd(int32_t V, const float *v_raw, const int32_t *vmesh, const float *mats, float *v_world, void *stream);
 int psdr_geo_world_vertices_rev(int32_t V, const float *v_raw, const int32_t *vmesh, const float *mats, const float *v_world, const float *a_world, float *a_raw,
                                 void *stream);
+/* t_world [V][3] from t_raw [V][3] and t_mats [M][16] (either may be null); v_world = the output of the forward entry. */
+int psdr_geo_world_vertices_jvp(int32_t V, const float *v_raw, const int32_t *vmesh, const float *mats, const float *v_world, const float *t_raw, const float *t_mats,
+                                float *t_world, void *stream);
 /* process_mesh (src/shape/mesh.cpp:20-51): rows = p0 e1 e2 n0 n1 n2 face_normal face_area with area-weighted vertex normals;
    vsum [V][3] = scratch kept for the adjoint (the un-normalised vertex normals). */
 int psdr_geo_tri_rows_fwd(int32_t V, int32_t T, const float *v, const int32_t *faces, float *vsum, float *rows, int32_t row_stride, void *stream);
 int psdr_geo_tri_rows_rev(int32_t V, int32_t T, const float *v, const int32_t *faces, const float *vsum, const float *a_rows, int32_t row_stride,
                           float *a_vsum /* scratch [V][3] */, float *a_v, void *stream);
+/* t_rows [T][row_stride] from t_v [V][3] (vsum: as the forward entry left it); the tangents of the vertex-normal sums are accumulated in
+   double like the sums themselves.  A degenerate face has zero face-normal and area tangents. */
+int psdr_geo_tri_rows_jvp(int32_t V, int32_t T, const float *v, const int32_t *faces, const float *vsum, const float *t_v, int32_t row_stride,
+                          float *t_vsum /* scratch [V][3] */, float *t_rows, void *stream);
 /* SecondaryEdgeInfo of EVERY candidate edge (Mesh::configure, mesh.cpp:251-270): info [E][16] = p0 e1 n0 n1 p2 is_boundary, and
    keep [E] = 1 where the coplanar filter of scene.cpp:219-244 keeps the edge (the caller compacts). */
 int psdr_geo_sec_edges_fwd(int32_t E, const int32_t *edges, const float *v, const float *rows, int32_t row_stride, float *info, uint8_t *keep, void *stream);
 int psdr_geo_sec_edges_rev(int32_t E, const int32_t *edges, const float *a_info, float *a_v, float *a_rows, int32_t row_stride, void *stream);
+/* t_info [E][16] from t_v [V][3] and t_rows [T][row_stride] (either may be null); a boundary edge's n1 tangent is zero. */
+int psdr_geo_sec_edges_jvp(int32_t E, const int32_t *edges, const float *t_v, const float *t_rows, int32_t row_stride, float *t_info, void *stream);
 /* PrimaryEdgeInfo of every candidate edge for one sensor (PerspectiveCamera::configure, src/sensor/perspective.cpp:39-111):
    cam22 = world_to_sample (16, row-major), camera position (3), viewing direction (3); face_normals [E] = 1 where the edge's mesh uses
    face normals; rows8 [E][PSDR_PEDGE_STRIDE], z4 [E][4] (psdr_scene_desc::prim_edge_z), keep [E] = the silhouette test. */
 int psdr_geo_prim_edges_fwd(int32_t E, const int32_t *edges, const uint8_t *face_normals, const float *v, const float *rows, int32_t row_stride,
                             const float *cam22, float *rows8, float *z4, uint8_t *keep, void *stream);
 int psdr_geo_prim_edges_rev(int32_t E, const int32_t *edges, const float *v, const float *cam22, const float *a_rows8, float *a_v, float *a_w2s /* [16] */,
+                            void *stream);
+/* t_rows8 [E][PSDR_PEDGE_STRIDE] from t_v [V][3] and t_w2s [16] (either may be null): the film positions' tangents; edge normal and length
+   come from detached end points (perspective.cpp) and get zero.  The rows enter only the silhouette test, so they take no tangent. */
+int psdr_geo_prim_edges_jvp(int32_t E, const int32_t *edges, const float *v, const float *cam22, const float *t_v, const float *t_w2s /* [16] */, float *t_rows8,
                             void *stream);
 
 /* The kept edges of a candidate table as a table of the SAME capacity, with the count left on the device (scene.cpp:219-244 and
@@ -339,10 +354,12 @@ int psdr_geo_prim_edges_rev(int32_t E, const int32_t *edges, const float *v, con
    (A = 0: none).  Outputs: rows_out [E][S] / aux_out [E][A] = the kept rows in their order, zero behind them; pos [E] = the new row of
    edge e or -1; pmf / cmf [E] = weight / sum and its running sum (cmf = 1 from the last kept row on, so a lower-bound search for u < 1
    never leaves the kept rows; the host passes sum = 1); header [2] = {number of kept rows as int bits, sum of the weights}.
-   scratch: 4 * ceil(E / 1024) words.  _rev WRITES a_rows [E][S] (the adjoint of rows) from a_rows_out. */
+   scratch: 4 * ceil(E / 1024) words.  _rev WRITES a_rows [E][S] (the adjoint of rows) from a_rows_out; _jvp WRITES t_rows_out [E][S]
+   (row pos[e] = t_rows row e, every other row zero). */
 int psdr_geo_compact_edges_fwd(int32_t E, const float *rows, int32_t S, const uint8_t *keep, int32_t w0, int32_t wn, const void *aux, int32_t aux_stride, int32_t A,
                                void *scratch, float *rows_out, void *aux_out, int32_t *pos, float *pmf, float *cmf, float *header, void *stream);
 int psdr_geo_compact_edges_rev(int32_t E, int32_t S, const int32_t *pos, const float *a_rows_out, float *a_rows, void *stream);
+int psdr_geo_compact_edges_jvp(int32_t E, int32_t S, const int32_t *pos, const float *t_rows, float *t_rows_out, void *stream);
 /* Mesh areas and the emitter tables (scene.cpp:183-196, area.cpp:10-16, mesh.cpp:244-249) without a host round trip: face_offset [M + 1],
    mesh_emitter [M] (-1: none), emitter_i [Ne][PSDR_EMITTER_I_STRIDE], radiance [Ne][3], env_weight [Ne] (< 0: an area light; otherwise the
    sampling weight of the environment map).  Outputs: mesh_area [M]; emitter_f [Ne][PSDR_EMITTER_F_STRIDE]; emitter_pmf / emitter_cmf [Ne]

@@ -1,7 +1,7 @@
 // psdr_tables.hip -- the differentiable table chain of Scene::configure as HIP kernels (round 3): world vertices -> TriangleInfo rows
 // (process_mesh, reference src/shape/mesh.cpp:20-51), secondary-edge records of every candidate edge (Mesh::configure, mesh.cpp:251-270 +
 // the coplanar filter of scene.cpp:219-244) and primary-edge records of every candidate edge of a sensor (perspective.cpp:39-111), each
-// with its hand-written adjoint.  One forward and one reverse entry point per table (include/psdr_hip.h psdr_geo_*); the host mirror wraps
+// with its hand-written adjoint and tangent.  One forward, one reverse and one forward-mode (jvp) entry point per table (include/psdr_hip.h psdr_geo_*); the host mirror wraps
 // them in torch.autograd.Function objects (psdr_cuda/tables_native.py).  Round 4: the compaction of the kept edges, their length
 // distributions, mesh areas and the emitter tables are kernels here as well (k_compact_*, k_mesh_areas, k_emitter_rows): no count or sum travels to the host.  Replaces ~150 eager torch launches per configure() and ~250 in its
 // backward.  Everything is fp32; the scatter-adds into vertex / row adjoints are hardware global_atomic_add_f32.
@@ -36,6 +36,12 @@ __device__ __forceinline__ void add3(float *p, V3 a) {
 }
 // y = x / |x|;  a_x = (a_y - y (y . a_y)) / |x|
 __device__ __forceinline__ V3 normalize_vjp(V3 y, float len, V3 ay) { const float inv = len > 0.f ? 1.f / len : 0.f; return (ay - y * dot(y, ay)) * inv; }
+// the same map in the tangent direction (the Jacobian (I - y y^T) / |x| is symmetric), from x itself: a zero x gives a zero tangent
+__device__ __forceinline__ V3 normalize_jvp(V3 x, V3 tx) {
+    const float len = sqrtf(dot(x, x)), inv = len > 0.f ? 1.f / len : 0.f;
+    const V3 y = x * inv;
+    return (tx - y * dot(y, tx)) * inv;
+}
 
 // ------------------------------------------------------------------ TriangleInfo rows (process_mesh, mesh.cpp:20-51)
 // pass 1: per face, the un-normalised normal cross(e1, e2) added to its three vertices (area-weighted vertex normals: mesh.cpp:33-41 sums
@@ -113,6 +119,43 @@ __global__ __launch_bounds__(kB) void k_tri_rows_rev(int T, const float *__restr
     add3(a_v + 3 * (size_t) i1, ae1); add3(a_v + 3 * (size_t) i2, ae2);
     add3(a_v + 3 * (size_t) i0, ld3(ar) - ae1 - ae2);
 }
+// tangent (forward mode), pass 1: per face, dc = de1 x e2 + e1 x de2 added to its three vertices -- in double and rounded once, as k_face_accum
+// sums c, so that the tangent of a vertex normal does not depend on the order the atomics land in either
+__global__ __launch_bounds__(kB) void k_face_accum_jvp(int T, const float *__restrict__ v, const int32_t *__restrict__ faces, const float *__restrict__ t_v,
+                                                       double *__restrict__ dsum) {
+    const int t = blockIdx.x * kB + threadIdx.x;
+    if (t >= T) return;
+    const int id[3] = {faces[3 * t], faces[3 * t + 1], faces[3 * t + 2]};
+    const V3 p0 = ld3(v + 3 * (size_t) id[0]), e1 = ld3(v + 3 * (size_t) id[1]) - p0, e2 = ld3(v + 3 * (size_t) id[2]) - p0;
+    const V3 d0 = ld3(t_v + 3 * (size_t) id[0]), de1 = ld3(t_v + 3 * (size_t) id[1]) - d0, de2 = ld3(t_v + 3 * (size_t) id[2]) - d0;
+    const V3 dc = cross(de1, e2) + cross(e1, de2);
+    for (int k = 0; k < 3; ++k) {
+        double *d = dsum + 3 * (size_t) id[k];
+        if (dc.x != 0.f) atomicAdd(d, (double) dc.x);
+        if (dc.y != 0.f) atomicAdd(d + 1, (double) dc.y);
+        if (dc.z != 0.f) atomicAdd(d + 2, (double) dc.z);
+    }
+}
+// tangent, pass 2: the rows' tangents.  A degenerate face (|c| = 0) has a zero face-normal tangent and a zero area tangent, a vertex whose
+// normal sum is zero a zero normal tangent: finite where the torch formulation divides by zero.
+__global__ __launch_bounds__(kB) void k_tri_rows_jvp(int T, const float *__restrict__ v, const int32_t *__restrict__ faces, const float *__restrict__ vsum,
+                                                     const float *__restrict__ t_v, const float *__restrict__ t_vsum, float *__restrict__ t_rows, int stride) {
+    const int t = blockIdx.x * kB + threadIdx.x;
+    if (t >= T) return;
+    const int id[3] = {faces[3 * t], faces[3 * t + 1], faces[3 * t + 2]};
+    const V3 p0 = ld3(v + 3 * (size_t) id[0]), e1 = ld3(v + 3 * (size_t) id[1]) - p0, e2 = ld3(v + 3 * (size_t) id[2]) - p0;
+    const V3 d0 = ld3(t_v + 3 * (size_t) id[0]), de1 = ld3(t_v + 3 * (size_t) id[1]) - d0, de2 = ld3(t_v + 3 * (size_t) id[2]) - d0;
+    const V3 c = cross(e1, e2), dc = cross(de1, e2) + cross(e1, de2);
+    const float len = sqrtf(dot(c, c)), inv = len > 0.f ? 1.f / len : 0.f;
+    const V3 fn = c * inv;
+    float *r = t_rows + (size_t) t * stride;
+    st3(r, d0); st3(r + 3, de1); st3(r + 6, de2);
+    for (int k = 0; k < 3; ++k) st3(r + 9 + 3 * k, normalize_jvp(ld3(vsum + 3 * (size_t) id[k]), ld3(t_vsum + 3 * (size_t) id[k])));
+    const float fdc = dot(fn, dc);
+    st3(r + 18, (dc - fn * fdc) * inv);
+    r[21] = 0.5f * fdc;
+    for (int k = 22; k < stride; ++k) r[k] = 0.f;
+}
 
 // -------------------------------------------------- secondary-edge records (mesh.cpp:251-270, scene.cpp:219-244)
 // edges[e] = v0, v1, face0, face1 (-1: boundary), opposite vertex of face0 (global ids).  info = p0 e1 n0 n1 p2 is_boundary; keep = the
@@ -139,6 +182,18 @@ __global__ __launch_bounds__(kB) void k_sec_edges_rev(int E, const int32_t *__re
     add3(a_v + 3 * (size_t) ed[0], ld3(a) - ae1); add3(a_v + 3 * (size_t) ed[1], ae1); add3(a_v + 3 * (size_t) ed[4], ld3(a + 12));
     add3(a_rows + (size_t) ed[2] * stride + 18, ld3(a + 6));
     if (ed[3] >= 0) add3(a_rows + (size_t) ed[3] * stride + 18, ld3(a + 9));
+}
+// tangent: the same gathers of the tangents (t_v / t_rows null = zero); a boundary edge has n1 = 0, so a zero n1 tangent
+__global__ __launch_bounds__(kB) void k_sec_edges_jvp(int E, const int32_t *__restrict__ edges, const float *__restrict__ t_v, const float *__restrict__ t_rows,
+                                                      int stride, float *__restrict__ t_info) {
+    const int e = blockIdx.x * kB + threadIdx.x;
+    if (e >= E) return;
+    const int32_t *ed = edges + 5 * (size_t) e;
+    const V3 z{0.f, 0.f, 0.f};
+    const V3 d0 = t_v ? ld3(t_v + 3 * (size_t) ed[0]) : z, de1 = t_v ? ld3(t_v + 3 * (size_t) ed[1]) - d0 : z, d2 = t_v ? ld3(t_v + 3 * (size_t) ed[4]) : z;
+    const V3 dn0 = t_rows ? ld3(t_rows + (size_t) ed[2] * stride + 18) : z, dn1 = t_rows && ed[3] >= 0 ? ld3(t_rows + (size_t) ed[3] * stride + 18) : z;
+    float *o = t_info + 16 * (size_t) e;
+    st3(o, d0); st3(o + 3, de1); st3(o + 6, dn0); st3(o + 9, dn1); st3(o + 12, d2); o[15] = 0.f;
 }
 
 // ------------------------------------------------------- primary-edge records of one sensor (perspective.cpp:39-111)
@@ -215,6 +270,30 @@ __global__ __launch_bounds__(kB) void k_prim_edges_rev(int E, const int32_t *__r
         if ((threadIdx.x & 63) == 0 && s != 0.f) atomicAdd(a_w2s + i, s);
     }
 }
+// tangent of q = (M p).xy / (M p).w:  dq = (dh.xy - q dw) / w,  dh = M dp + dM p  (rows 0, 1, 3; dp / dm null = zero)
+__device__ __forceinline__ void project_jvp(const float *m, V3 p, V3 dp, const float *dm, float &dqx, float &dqy) {
+    float qx, qy, iw;
+    project(m, p, qx, qy, iw);
+    float dhx = m[0] * dp.x + m[1] * dp.y + m[2] * dp.z, dhy = m[4] * dp.x + m[5] * dp.y + m[6] * dp.z, dw = m[12] * dp.x + m[13] * dp.y + m[14] * dp.z;
+    if (dm) {
+        dhx += dm[0] * p.x + dm[1] * p.y + dm[2] * p.z + dm[3];
+        dhy += dm[4] * p.x + dm[5] * p.y + dm[6] * p.z + dm[7];
+        dw += dm[12] * p.x + dm[13] * p.y + dm[14] * p.z + dm[15];
+    }
+    dqx = (dhx - qx * dw) * iw; dqy = (dhy - qy * dw) * iw;
+}
+// the film positions carry the tangent; edge normal and length are taken from detached q0 / q1 (perspective.cpp) and carry none
+__global__ __launch_bounds__(kB) void k_prim_edges_jvp(int E, const int32_t *__restrict__ edges, const float *__restrict__ v, const float *__restrict__ cam,
+                                                       const float *__restrict__ t_v, const float *__restrict__ t_w2s, float *__restrict__ t_rows8) {
+    const int e = blockIdx.x * kB + threadIdx.x;
+    if (e >= E) return;
+    const int32_t *ed = edges + 5 * (size_t) e;
+    const V3 z{0.f, 0.f, 0.f};
+    float *o = t_rows8 + 8 * (size_t) e;
+    project_jvp(cam, ld3(v + 3 * (size_t) ed[0]), t_v ? ld3(t_v + 3 * (size_t) ed[0]) : z, t_w2s, o[0], o[1]);
+    project_jvp(cam, ld3(v + 3 * (size_t) ed[1]), t_v ? ld3(t_v + 3 * (size_t) ed[1]) : z, t_w2s, o[2], o[3]);
+    o[4] = 0.f; o[5] = 0.f; o[6] = 0.f; o[7] = 0.f;
+}
 
 // ------------------------------------------------------------------------------ world positions
 // transform_pos (include/psdr/core/transform.h:84-88) of every vertex by ITS mesh's to_world matrix: y = (A v + t) / (p . v + q).  Products and
@@ -249,6 +328,26 @@ __global__ __launch_bounds__(kB) void k_world_vertices_rev(int V, const float *_
     const float w = m[12] * x.x + m[13] * x.y + m[14] * x.z + m[15], iw = 1.f / w, ya = dot(yy, a);
     st3(a_raw + 3 * (size_t) i, V3{(m[0] * a.x + m[4] * a.y + m[8] * a.z - m[12] * ya) * iw, (m[1] * a.x + m[5] * a.y + m[9] * a.z - m[13] * ya) * iw,
                                    (m[2] * a.x + m[6] * a.y + m[10] * a.z - m[14] * ya) * iw});
+}
+// tangent: dy = (dh - y dw) / w with dh = A dx + dA x + dt, dw = p . dx + dp . x + dq (t_raw / t_mats null = zero)
+__global__ __launch_bounds__(kB) void k_world_vertices_jvp(int V, const float *__restrict__ v_raw, const int32_t *__restrict__ vmesh, const float *__restrict__ mats,
+                                                           const float *__restrict__ y, const float *__restrict__ t_raw, const float *__restrict__ t_mats,
+                                                           float *__restrict__ t_y) {
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (i >= V) return;
+    const float *m = mats + 16 * (size_t) vmesh[i];
+    const V3 x = ld3(v_raw + 3 * (size_t) i), yy = ld3(y + 3 * (size_t) i);
+    const float w = m[12] * x.x + m[13] * x.y + m[14] * x.z + m[15], iw = 1.f / w;
+    float dh[4] = {0.f, 0.f, 0.f, 0.f};
+    if (t_raw) {
+        const V3 dx = ld3(t_raw + 3 * (size_t) i);
+        for (int r = 0; r < 4; ++r) dh[r] = m[4 * r] * dx.x + m[4 * r + 1] * dx.y + m[4 * r + 2] * dx.z;
+    }
+    if (t_mats) {
+        const float *dm = t_mats + 16 * (size_t) vmesh[i];
+        for (int r = 0; r < 4; ++r) dh[r] += dm[4 * r] * x.x + dm[4 * r + 1] * x.y + dm[4 * r + 2] * x.z + dm[4 * r + 3];
+    }
+    st3(t_y + 3 * (size_t) i, (V3{dh[0], dh[1], dh[2]} - yy * dh[3]) * iw);
 }
 
 // ------------------------------------------------------------- kept edges -> table + length distribution, count on the device
@@ -342,6 +441,13 @@ __global__ __launch_bounds__(kB) void k_compact_rev(int E, int S, const int32_t 
     const int e = (int) (i / S), c = (int) (i - (long long) e * S), p = pos[e];
     a_rows[i] = p >= 0 ? a_out[(size_t) p * S + c] : 0.f;
 }
+// tangent: row e of the tangent lands where its row went (the caller's memset zeroes the tail and the rows nothing lands in)
+__global__ __launch_bounds__(kB) void k_compact_jvp(int E, int S, const int32_t *__restrict__ pos, const float *__restrict__ t_rows, float *__restrict__ t_out) {
+    const long long i = (long long) blockIdx.x * kB + threadIdx.x;
+    if (i >= (long long) E * S) return;
+    const int e = (int) (i / S), c = (int) (i - (long long) e * S), p = pos[e];
+    if (p >= 0) t_out[(size_t) p * S + c] = t_rows[i];
+}
 
 // ------------------------------------------------------------------ mesh areas + emitter tables (scene.cpp:183-196, area.cpp:10-16)
 // One workgroup per mesh: its total area (Mesh::m_total_area, mesh.cpp:244-246) and, for the mesh of an area light, the face-area
@@ -411,6 +517,13 @@ int psdr_geo_world_vertices_rev(int32_t V, const float *v_raw, const int32_t *vm
     TAB_TRY(hipGetLastError());
     return 0;
 }
+int psdr_geo_world_vertices_jvp(int32_t V, const float *v_raw, const int32_t *vmesh, const float *mats, const float *v_world, const float *t_raw, const float *t_mats,
+                                float *t_world, void *stream) {
+    if (V <= 0 || !v_raw || !vmesh || !mats || !v_world || !t_world) return psdr_host::fail("psdr_geo_world_vertices_jvp: invalid argument");
+    hipLaunchKernelGGL(k_world_vertices_jvp, grid(V), dim3(kB), 0, (hipStream_t) stream, V, v_raw, vmesh, mats, v_world, t_raw, t_mats, t_world);
+    TAB_TRY(hipGetLastError());
+    return 0;
+}
 int psdr_geo_tri_rows_fwd(int32_t V, int32_t T, const float *v, const int32_t *faces, float *vsum, float *rows, int32_t row_stride, void *stream) {
     if (V <= 0 || T <= 0 || !v || !faces || !vsum || !rows || row_stride < 22) return psdr_host::fail("psdr_geo_tri_rows_fwd: invalid argument");
     hipStream_t s = (hipStream_t) stream;
@@ -438,6 +551,23 @@ int psdr_geo_tri_rows_rev(int32_t V, int32_t T, const float *v, const int32_t *f
     TAB_TRY(hipGetLastError());
     return 0;
 }
+int psdr_geo_tri_rows_jvp(int32_t V, int32_t T, const float *v, const int32_t *faces, const float *vsum, const float *t_v, int32_t row_stride, float *t_vsum,
+                          float *t_rows, void *stream) {
+    if (V <= 0 || T <= 0 || !v || !faces || !vsum || !t_v || !t_vsum || !t_rows || row_stride < 22) return psdr_host::fail("psdr_geo_tri_rows_jvp: invalid argument");
+    hipStream_t s = (hipStream_t) stream;
+    // the double accumulators of the normal-sum tangents live in the tangent rows until those are written (as in psdr_geo_tri_rows_fwd)
+    const size_t acc_bytes = sizeof(double) * 3 * (size_t) V;
+    double *dsum = reinterpret_cast<double *>(t_rows);
+    const bool own = acc_bytes > sizeof(float) * (size_t) row_stride * (size_t) T || (reinterpret_cast<uintptr_t>(t_rows) & 7u) != 0;
+    if (own) TAB_TRY(hipMallocAsync(reinterpret_cast<void **>(&dsum), acc_bytes, s));
+    TAB_TRY(hipMemsetAsync(dsum, 0, acc_bytes, s));
+    hipLaunchKernelGGL(k_face_accum_jvp, grid(T), dim3(kB), 0, s, T, v, faces, t_v, dsum);
+    hipLaunchKernelGGL(k_vsum_round, grid(3 * V), dim3(kB), 0, s, 3 * V, dsum, t_vsum);
+    if (own) TAB_TRY(hipFreeAsync(dsum, s));
+    hipLaunchKernelGGL(k_tri_rows_jvp, grid(T), dim3(kB), 0, s, T, v, faces, vsum, t_v, t_vsum, t_rows, row_stride);
+    TAB_TRY(hipGetLastError());
+    return 0;
+}
 int psdr_geo_sec_edges_fwd(int32_t E, const int32_t *edges, const float *v, const float *rows, int32_t row_stride, float *info, uint8_t *keep, void *stream) {
     if (E <= 0 || !edges || !v || !rows || !info || !keep) return psdr_host::fail("psdr_geo_sec_edges_fwd: invalid argument");
     hipLaunchKernelGGL(k_sec_edges, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, v, rows, row_stride, info, keep);
@@ -447,6 +577,12 @@ int psdr_geo_sec_edges_fwd(int32_t E, const int32_t *edges, const float *v, cons
 int psdr_geo_sec_edges_rev(int32_t E, const int32_t *edges, const float *a_info, float *a_v, float *a_rows, int32_t row_stride, void *stream) {
     if (E <= 0 || !edges || !a_info || !a_v || !a_rows) return psdr_host::fail("psdr_geo_sec_edges_rev: invalid argument");
     hipLaunchKernelGGL(k_sec_edges_rev, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, a_info, a_v, a_rows, row_stride);
+    TAB_TRY(hipGetLastError());
+    return 0;
+}
+int psdr_geo_sec_edges_jvp(int32_t E, const int32_t *edges, const float *t_v, const float *t_rows, int32_t row_stride, float *t_info, void *stream) {
+    if (E <= 0 || !edges || !t_info || (t_rows && row_stride < 22)) return psdr_host::fail("psdr_geo_sec_edges_jvp: invalid argument");
+    hipLaunchKernelGGL(k_sec_edges_jvp, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, t_v, t_rows, row_stride, t_info);
     TAB_TRY(hipGetLastError());
     return 0;
 }
@@ -460,6 +596,12 @@ int psdr_geo_prim_edges_fwd(int32_t E, const int32_t *edges, const uint8_t *face
 int psdr_geo_prim_edges_rev(int32_t E, const int32_t *edges, const float *v, const float *cam22, const float *a_rows8, float *a_v, float *a_w2s, void *stream) {
     if (E <= 0 || !edges || !v || !cam22 || !a_rows8 || !a_v || !a_w2s) return psdr_host::fail("psdr_geo_prim_edges_rev: invalid argument");
     hipLaunchKernelGGL(k_prim_edges_rev, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, v, cam22, a_rows8, a_v, a_w2s);
+    TAB_TRY(hipGetLastError());
+    return 0;
+}
+int psdr_geo_prim_edges_jvp(int32_t E, const int32_t *edges, const float *v, const float *cam22, const float *t_v, const float *t_w2s, float *t_rows8, void *stream) {
+    if (E <= 0 || !edges || !v || !cam22 || !t_rows8) return psdr_host::fail("psdr_geo_prim_edges_jvp: invalid argument");
+    hipLaunchKernelGGL(k_prim_edges_jvp, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, v, cam22, t_v, t_w2s, t_rows8);
     TAB_TRY(hipGetLastError());
     return 0;
 }
@@ -484,6 +626,15 @@ int psdr_geo_compact_edges_rev(int32_t E, int32_t S, const int32_t *pos, const f
     if (E <= 0 || S <= 0 || !pos || !a_rows_out || !a_rows) return psdr_host::fail("psdr_geo_compact_edges_rev: invalid argument");
     const long long n = (long long) E * S;
     hipLaunchKernelGGL(k_compact_rev, dim3((unsigned) ((n + kB - 1) / kB)), dim3(kB), 0, (hipStream_t) stream, E, S, pos, a_rows_out, a_rows);
+    TAB_TRY(hipGetLastError());
+    return 0;
+}
+int psdr_geo_compact_edges_jvp(int32_t E, int32_t S, const int32_t *pos, const float *t_rows, float *t_rows_out, void *stream) {
+    if (E <= 0 || S <= 0 || !pos || !t_rows || !t_rows_out) return psdr_host::fail("psdr_geo_compact_edges_jvp: invalid argument");
+    hipStream_t s = (hipStream_t) stream;
+    const long long n = (long long) E * S;
+    TAB_TRY(hipMemsetAsync(t_rows_out, 0, sizeof(float) * (size_t) n, s));
+    hipLaunchKernelGGL(k_compact_jvp, dim3((unsigned) ((n + kB - 1) / kB)), dim3(kB), 0, s, E, S, pos, t_rows, t_rows_out);
     TAB_TRY(hipGetLastError());
     return 0;
 }

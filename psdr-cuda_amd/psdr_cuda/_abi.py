@@ -87,6 +87,7 @@ HIP_SYMBOLS = (
     "psdr_guide_build", "psdr_get_counters",
     "psdr_geo_world_vertices_fwd", "psdr_geo_world_vertices_rev", "psdr_geo_tri_rows_fwd", "psdr_geo_tri_rows_rev", "psdr_geo_sec_edges_fwd", "psdr_geo_sec_edges_rev", "psdr_geo_prim_edges_fwd", "psdr_geo_prim_edges_rev",
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
+    "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
 )
 
 HIP_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libpsdr_hip.so")   # the in-tree build; the package reads NO environment variable
@@ -138,6 +139,11 @@ def load_hip():
     lib.psdr_geo_prim_edges_rev.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
     lib.psdr_geo_compact_edges_fwd.argtypes = [i32, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.psdr_geo_compact_edges_rev.argtypes = [i32, i32, vp, vp, vp, vp]
+    lib.psdr_geo_world_vertices_jvp.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.psdr_geo_tri_rows_jvp.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.psdr_geo_sec_edges_jvp.argtypes = [i32, vp, vp, vp, i32, vp, vp]
+    lib.psdr_geo_prim_edges_jvp.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.psdr_geo_compact_edges_jvp.argtypes = [i32, i32, vp, vp, vp, vp]
     lib.psdr_geo_emitter_tables.argtypes = [i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in HIP_SYMBOLS:
         if name not in ("psdr_last_error", "psdr_version"):

@@ -363,15 +363,8 @@ class PerspectiveCamera(Sensor):
             ei = bt["tp"]["edges"]
             if ei is not None and tables_native.available(bt["v_world"]):
                 # every candidate edge in ONE launch (csrc/psdr_tables.hip k_prim_edges): film records, 1 / depth rows, silhouette test
-                def film_records(v, m, edges):
-                    edges = edges.long()
-                    q0, q1 = transform_pos(m, v.index_select(0, edges[:, 0]))[:, :2], transform_pos(m, v.index_select(0, edges[:, 1]))[:, :2]
-                    e = (q1 - q0).detach()
-                    ln = torch.sqrt((e * e).sum(-1))
-                    e = e / ln.unsqueeze(-1)
-                    return torch.cat([q0, q1, torch.stack([-e[:, 1], e[:, 0]], dim=-1), ln.unsqueeze(-1), torch.zeros_like(ln).unsqueeze(-1)], dim=-1)
                 r8, z4, keep8 = tables_native.prim_edges(bt["v_world"], w2s, bt["tri_info"], bt["tp"]["edges_i32"], bt["tp"]["edge_face_normals_u8"],
-                                                        cam_pos, cam_dir, film_records, cam22=cam[32:54])
+                                                        cam_pos, cam_dir, primary_edge_records, cam22=cam[32:54])
                 # the kept edges first, in a table of the same capacity; their number and the sum of their lengths stay on the device
                 # (csrc/psdr_tables.hip k_compact_*): no read-back, no host-sized gather
                 pe, zs, _pos, pmf, cmf, hdr = tables_native.compact_edges(r8, keep8, 6, 1, aux=z4, aux_cols=4)
@@ -522,6 +515,30 @@ def build_edge_indices(faces, fname="<mesh>"):
     if (out[two, 2] == out[two, 3]).any():
         raise RuntimeError("Duplicated faces: " + fname)
     return out
+
+
+def primary_edge_records(v, m, edges):
+    """the film records of every candidate edge (perspective.cpp:39-111) as the kernels write them (rows8): end points on the film, then the
+    edge normal and length from DETACHED end points, 0 -- the torch formulation of tables_native.prim_edges"""
+    edges = edges.long()
+    q0, q1 = transform_pos(m, v.index_select(0, edges[:, 0]))[:, :2], transform_pos(m, v.index_select(0, edges[:, 1]))[:, :2]
+    e = (q1 - q0).detach()
+    ln = torch.sqrt((e * e).sum(-1))
+    e = e / ln.unsqueeze(-1)
+    return torch.cat([q0, q1, torch.stack([-e[:, 1], e[:, 0]], dim=-1), ln.unsqueeze(-1), torch.zeros_like(ln).unsqueeze(-1)], dim=-1)
+
+
+def secondary_edge_records(v, rows, edges):
+    """SecondaryEdgeInfo of every candidate edge (mesh.cpp:251-270): p0 e1 n0 n1 p2 is_boundary [E,16] (n1 = 0 on a boundary edge)"""
+    edges = edges.long()
+    is_b = edges[:, 3] < 0
+    fnr = rows[:, 18:21]
+    p0 = v.index_select(0, edges[:, 0])
+    e1 = v.index_select(0, edges[:, 1]) - p0
+    n0 = fnr.index_select(0, edges[:, 2])
+    n1 = fnr.index_select(0, torch.where(is_b, torch.zeros_like(edges[:, 3]), edges[:, 3])) * (~is_b).unsqueeze(-1).to(torch.float32)
+    p2 = v.index_select(0, edges[:, 4])
+    return torch.cat([p0, e1, n0, n1, p2, is_b.to(torch.float32).unsqueeze(-1)], dim=-1)
 
 
 def process_mesh(verts, faces):
@@ -1192,22 +1209,11 @@ class Scene(Object):
         ei = tp["edges"]
         if ei is None:
             return None
-
-        def records(v, rows, edges):
-            edges = edges.long()
-            is_b = edges[:, 3] < 0
-            fnr = rows[:, 18:21]
-            p0 = v.index_select(0, edges[:, 0])
-            e1 = v.index_select(0, edges[:, 1]) - p0
-            n0 = fnr.index_select(0, edges[:, 2])
-            n1 = fnr.index_select(0, torch.where(is_b, torch.zeros_like(edges[:, 3]), edges[:, 3])) * (~is_b).unsqueeze(-1).to(torch.float32)
-            p2 = v.index_select(0, edges[:, 4])
-            return torch.cat([p0, e1, n0, n1, p2, is_b.to(torch.float32).unsqueeze(-1)], dim=-1)
         if tables_native.available(v_world):
-            info, keep8 = tables_native.sec_edges(v_world, tri_info, tp["edges_i32"], records)
+            info, keep8 = tables_native.sec_edges(v_world, tri_info, tp["edges_i32"], secondary_edge_records)
             return info, keep8          # _finish_native compacts on the device
         else:
-            info = records(v_world, tri_info, ei)
+            info = secondary_edge_records(v_world, tri_info, ei)
             is_b = ei[:, 3] < 0           # (the filter on the gathered normals themselves, as this chain always evaluated it: the rounding of the
             n0 = tri_info[ei[:, 2], 18:21]     # reduction depends on the memory layout of its operand, and the committed fixtures follow these decisions)
             n1 = tri_info[torch.where(is_b, torch.zeros_like(ei[:, 3]), ei[:, 3]), 18:21] * (~is_b).unsqueeze(-1).to(torch.float32)
