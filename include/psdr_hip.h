@@ -369,6 +369,18 @@ int psdr_geo_emitter_tables(int32_t M, const float *rows, int32_t row_stride, co
                             const float *radiance, const float *env_weight, float *mesh_area, float *emitter_f, float *emitter_pmf, float *emitter_cmf, float *face_pmf,
                             float *face_cmf, void *stream);
 
+/* Gradient layout of the last psdr_render_d_rev on this handle (diagnostics: which destination each adjoint of the camera
+   term went to; zeros before the first call).  out = {
+     [0] texel words cached in LDS (0: global atomics), [1] emitter-radiance words cached, [2] environment-map words cached,
+     [3] triangle rows cached (the rest go through global atomics), [4] copies of the LDS cache,
+     [5] lane-private emitter rows, [6] 1 if those live in registers, [7] deferred row columns per lane,
+     [8] camera launch: -1 none, 0 one kernel, 1 value + adjoint kernel, 2 the same with the wavefront value sweep, 3 adjoint kernel
+         on kept records, 4 probe pass + reverse kernel,
+     [9] copies of the primary-edge table (0: no primary-edge launch), [10] 1 if cached rows are addressed by triangle (slot = triangle),
+     [11] 1 if the path records live in HBM, [12] [13] cache slots of the private rows, [14] hot rows the tree build chose,
+     [15] 1 if the primary-edge slots ran sorted by pixel } */
+int psdr_scene_rev_layout(psdr_scene_t h, int32_t out[16]);
+
 /* Counters of the last render call on this handle (host values):
    [0] rays traced, [1] camera slots, [2] primary-edge slots, [3] secondary-edge slots. */
 int psdr_get_counters(psdr_scene_t h, uint64_t out[4]);

@@ -1382,6 +1382,8 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
         return fail("psdr_render_d_rev: PathTracer max_depth > 250 is not supported in reverse mode");
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
+    std::fill(std::begin(h->rev_layout), std::end(h->rev_layout), 0);
+    h->rev_layout[8] = -1;                                                // (no camera launch)
     return variant_of(h)->render_rev(h, o, adj_img, out_img, grads, s);
 }
 
@@ -1412,6 +1414,12 @@ int psdr_scene_info(psdr_scene_t h, int32_t out[8]) {
     const int n_slab = (h->aa_cnt & 255) + ((h->aa_cnt >> 8) & 255) + (h->aa_cnt >> 16);
     out[0] = h->n_tiny - (h->aa_cnt != 0 ? kAaSlots - n_slab : 0); out[1] = h->n_blas; out[2] = h->n_inline; out[3] = h->num_btris; out[4] = h->lbvh ? 1 : 0;
     out[5] = n_slab; out[6] = h->have_occ ? 1 : 0; out[7] = h->have_occ ? h->occ_max_rows : 0;
+    return 0;
+}
+
+int psdr_scene_rev_layout(psdr_scene_t h, int32_t out[16]) {
+    if (!h || !out) return fail("psdr_scene_rev_layout: null argument");
+    std::copy(std::begin(h->rev_layout), std::end(h->rev_layout), out);
     return 0;
 }
 

@@ -233,6 +233,8 @@ struct psdr_scene_s {
     hipStream_t refit_stream = nullptr;    // stream of the last device refit
     uint64_t slots[3] = {0, 0, 0};
     int last_path_depth = 0;
+    // gradient layout of the last psdr_render_d_rev on this handle (psdr_scene_rev_layout; render_rev fills it)
+    int32_t rev_layout[16] = {};
 
     // reverse-mode gradient sink: triangle rows cached in LDS (chosen at build time)
     std::vector<int32_t> emitter_i;        // host copy of desc.emitter_i (the emitter meshes' rows are hot)

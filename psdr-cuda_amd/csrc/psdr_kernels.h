@@ -2244,6 +2244,12 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
             }
         }
         const int cache_bytes = sink_bytes(sink.L);
+        {
+            int32_t *r = h->rev_layout;                                 // psdr_scene_rev_layout
+            r[0] = sink.L.tex_n; r[1] = sink.L.rad_n; r[2] = sink.L.env_n; r[3] = sink.L.hot_rows; r[4] = sink.L.rep;
+            r[5] = sink.L.priv_rows; r[6] = sink.L.priv_regs; r[7] = sink.L.pend_rows;
+            r[10] = h->hot_identity ? 1 : 0; r[11] = deep_rec ? 1 : 0; r[12] = sink.L.priv_slot[0]; r[13] = sink.L.priv_slot[1]; r[14] = h->hot_rows;
+        }
         plan_lds(h, cx, split ? rec_bytes : rec_bytes + cache_bytes);   // stage less of the scene: the record (+ cache) live in LDS too
         cx.off_pathrec = lds_bytes(cx, h);
         cx.off_sink = cx.off_pathrec + rec_bytes;
@@ -2272,6 +2278,7 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
         const int disk_cf = wf_value ? 1 : 0;
         bool direct_probe = false;
         if constexpr ((FL & kSceneForest) != 0) direct_probe = !split && !no_tree && o->integrator == PSDR_INTEGRATOR_DIRECT && probe_direct(h, o, n);
+        h->rev_layout[8] = split ? (wf_value ? 2 : 1) : direct_probe ? 4 : 0;
         if (split) {
             // records of one chunk of slots live in a scratch buffer (2 + 5 depth words per slot; 2 + 8 depth from the wavefront); chunks bound its size
             const int words = kRevDiskHead + (wf_value ? kRevDiskPerVertexCf : kRevDiskPerVertex) * depth;
@@ -2288,6 +2295,7 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
             const bool reuse = (wf_value ? h->kept.kind == 1 : kept_fused) && h->kept.valid && h->kept.gen == h->tables_gen && h->kept.n == n && chunk >= n && out_img == nullptr &&
                                same_camera_samples(h->kept.o, *o) && need <= h->rev_bytes;
             if (!reuse) h->kept.valid = false;          // this launch overwrites them
+            else h->rev_layout[8] = 3;
             for (long long c0 = 0; c0 < n; c0 += chunk) {
                 const long long nc = std::min(chunk, n - c0);
                 if (o->integrator == PSDR_INTEGRATOR_PATH) {
@@ -2376,6 +2384,7 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
         const PrimaryEdgeSink<FL> pe_sink{reps > 1 ? reinterpret_cast<float *>(h->d_pe_rep) : grads->g_prim_edge, pe_words, reps};
         const uint32_t *order = nullptr;
         if (int rc = primary_edge_order(h, cx, i0, n, &order, s)) return rc;
+        h->rev_layout[9] = reps; h->rev_layout[15] = order != nullptr ? 1 : 0;
 #define PSDR_LAUNCH_PER(INTEG)                                                                                                       \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_primary_edge_rev<FL, INTEG>), dim3(launch_blocks(h, n, big_launch_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, pe_sink, i0, n, \
                            1.f / (float) o->sppe, adj_img, h->d_counters, order)

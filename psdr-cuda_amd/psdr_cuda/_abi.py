@@ -84,7 +84,7 @@ TANGENT_FIELDS = ("tri_info", "texels", "emitter_rad", "cam_to_world", "sec_edge
 HIP_SYMBOLS = (
     "psdr_last_error", "psdr_version", "psdr_abi_struct_sizes", "psdr_scene_create", "psdr_scene_destroy", "psdr_scene_set_option", "psdr_scene_set_tables",
     "psdr_bvh_build", "psdr_bvh_stats", "psdr_scene_info", "psdr_trace", "psdr_render_c", "psdr_render_d_fwd", "psdr_render_d_rev",
-    "psdr_guide_build", "psdr_get_counters",
+    "psdr_guide_build", "psdr_get_counters", "psdr_scene_rev_layout",
     "psdr_geo_world_vertices_fwd", "psdr_geo_world_vertices_rev", "psdr_geo_tri_rows_fwd", "psdr_geo_tri_rows_rev", "psdr_geo_sec_edges_fwd", "psdr_geo_sec_edges_rev", "psdr_geo_prim_edges_fwd", "psdr_geo_prim_edges_rev",
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
     "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
@@ -129,6 +129,7 @@ def load_hip():
     lib.psdr_guide_build.argtypes = [vp, C.POINTER(RenderOpts), C.POINTER(i32), i32, vp, vp]
     lib.psdr_get_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.psdr_scene_info.argtypes = [vp, C.POINTER(i32)]
+    lib.psdr_scene_rev_layout.argtypes = [vp, C.POINTER(i32)]
     lib.psdr_geo_world_vertices_fwd.argtypes = [i32, vp, vp, vp, vp, vp]
     lib.psdr_geo_world_vertices_rev.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
     lib.psdr_geo_tri_rows_fwd.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
@@ -169,6 +170,20 @@ def scene_stats(handle):
     out = (C.c_int32 * 8)()
     check(lib, lib.psdr_scene_info(handle, out))
     return {"n_tiny": out[0], "n_blas": out[1], "n_inline": out[2], "leaf_tris": out[3], "device_built": out[4], "n_slab": out[5], "occ_rows": out[6], "occ_max_rows": out[7]}
+
+
+REV_LAUNCH_KINDS = {-1: "none", 0: "fused", 1: "split", 2: "split_wavefront", 3: "kept_records", 4: "probe"}
+
+
+def rev_layout(handle):
+    """psdr_scene_rev_layout as a dict: where the adjoints of the handle's last psdr_render_d_rev went (LDS cache arms, private and deferred rows,
+    camera launch form, primary-edge table copies)."""
+    lib = load_hip()
+    out = (C.c_int32 * 16)()
+    check(lib, lib.psdr_scene_rev_layout(handle, out))
+    return {"tex_n": out[0], "rad_n": out[1], "env_n": out[2], "hot_rows": out[3], "rep": out[4], "priv_rows": out[5], "priv_regs": out[6],
+            "pend_rows": out[7], "launch": REV_LAUNCH_KINDS[out[8]], "pe_reps": out[9], "hot_identity": out[10], "deep_rec": out[11],
+            "priv_slot": (out[12], out[13]), "tree_hot_rows": out[14], "pe_sorted": out[15]}
 
 
 def make_opts(integrator=INTEGRATOR_DIRECT, bsdf_samples=1, light_samples=1, max_depth=1, hide_emitters=False,

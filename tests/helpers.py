@@ -157,6 +157,70 @@ def host_render_rev(tb, opts, adj, want=AD_KEYS, guide=None):
     return img.reshape(-1, 3), bufs
 
 
+def host_render_rev_f64(tb, opts, adj, want=AD_KEYS):
+    """Reverse mode of the product code on the host with every gradient entry accumulated in DOUBLE: returns (img, {table: (sum, abs_sum)}),
+    sum = the entry's gradient, abs_sum = the sum of the magnitudes of the fp32 pieces it is made of (the scale an fp32 sum of the entry is judged by)."""
+    H = hostcheck_lib()
+    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
+    desc, keep = make_desc(tbc, None, device="cpu")
+    sums, abss = (C.c_void_p * 7)(), (C.c_void_p * 7)()
+    out = {}
+    for i, name in enumerate(_abi.TANGENT_FIELDS):
+        t = tbc.get(name)
+        if name not in want or t is None:
+            continue
+        out[name] = (np.zeros(tuple(t.shape), np.float64), np.zeros(tuple(t.shape), np.float64))
+        sums[i], abss[i] = out[name][0].ctypes.data, out[name][1].ctypes.data
+    adj = np.ascontiguousarray(adj, dtype=np.float32).reshape(-1)
+    img = np.zeros(adj.shape[0], np.float32)
+    rc = H.hostcheck_render_rev_f64(C.byref(desc), C.byref(opts), C.c_void_p(adj.ctypes.data), C.c_void_p(img.ctypes.data), sums, abss)
+    assert rc == 0
+    return img.reshape(-1, 3), out
+
+
+def entry_errors(a, ref, c, floor_rel):
+    """Per-entry comparison of an fp32 gradient table `a` with the double reference `ref` = (sum, abs_sum):
+        |a - sum|  <=  c eps32 abs_sum  +  floor_rel max(abs_sum)
+    Returns (ratio, bad): the worst ratio of |a - sum| to that bound (<= 1 passes) and the mask of the entries above it."""
+    s, sa = (np.asarray(x, np.float64).reshape(-1) for x in ref)
+    a = np.asarray(a, np.float64).reshape(-1)
+    bound = c * float(np.finfo(np.float32).eps) * sa + floor_rel * max(float(sa.max(initial=0.0)), 1e-30)
+    d = np.abs(a - s)
+    # (an entry no piece reaches has a zero bound: it passes only if it is zero)
+    r = np.divide(d, bound, out=np.where(d > 0, np.inf, 0.0), where=bound > 0)
+    return float(r.max(initial=0.0)), r > 1.0
+
+
+def outlier_share(a, ref, bad):
+    """The largest share of its OWN magnitude sum an outlier entry is off by, |a - sum| / abs_sum (0 without outliers).  A flipped sample moves one piece of
+    an entry; an entry that is dropped, or lands in another slot, moves by all of |sum| -- for an entry of one-signed pieces, its whole abs_sum."""
+    s, sa = (np.asarray(x, np.float64).reshape(-1) for x in ref)
+    bad = np.asarray(bad).reshape(-1) & (sa > 0)
+    if not bad.any():
+        return 0.0
+    return float((np.abs(np.asarray(a, np.float64).reshape(-1) - s)[bad] / sa[bad]).max())
+
+
+def excluded_entries_unbiased(a, ref, bad, label="", max_share=None):
+    """The net under the outliers of a per-entry comparison (as isolated_pixels_unbiased for pixels): the excluded entries' SIGNED error against the reference
+    must be consistent with independent flips of random sign, |sum_bad (a - sum)| <= 3 sqrt(sum_bad (a - sum)^2) + 1e-6 sum abs_sum, and negligible against
+    the table, <= 1e-3 sum abs_sum.  A defect confined to a few entries (a dropped row, a slot that always loses) is one-signed on them.  max_share: no
+    outlier may be off by more than this share of its own abs_sum (outlier_share) -- a defect that zeroes a small entry is not a flip."""
+    s, sa = (np.asarray(x, np.float64).reshape(-1) for x in ref)
+    if max_share is not None:
+        sh = outlier_share(a, ref, bad)
+        assert sh <= max_share, "%s: an outlier entry is off by %.2f of its own magnitude sum (a flip moves a piece of an entry, not all of it)" % (label, sh)
+    e = (np.asarray(a, np.float64).reshape(-1) - s)[np.asarray(bad).reshape(-1)]
+    if e.size < 2:
+        # one entry is no statistic: it must be negligible against its table
+        assert e.size == 0 or abs(e.sum()) <= 1e-3 * sa.sum(), "%s: the outlier entry is off by %.3e of the table" % (label, abs(e.sum()) / sa.sum())
+        return
+    tot = sa.sum() + 1e-30
+    assert abs(e.sum()) <= 3.0 * np.sqrt((e * e).sum()) + 1e-6 * tot, "%s: the %d outlier entries are biased: signed sum %.3e, 3 sigma %.3e" % (
+        label, e.size, e.sum(), 3.0 * np.sqrt((e * e).sum()))
+    assert abs(e.sum()) <= 1e-3 * tot, "%s: the %d outlier entries carry %.2e of the table in one direction" % (label, e.size, abs(e.sum()) / tot)
+
+
 def random_tangents(tb, names, seed=0):
     g = torch.Generator().manual_seed(seed)
     out = {}

@@ -243,15 +243,14 @@ struct HostSink {
     void add_sedge(int e, int w, float v) const { put(g.g_sec_edge, (size_t) e * PSDR_SEDGE_STRIDE + w, v); }
     void add_pedge(int e, int w, float v) const { put(g.g_prim_edge, (size_t) e * PSDR_PEDGE_STRIDE + w, v); }
 };
-}  // namespace
-
-extern "C" int hostcheck_render_rev(const psdr_scene_desc *d, const psdr_render_opts *o, const float *adj, float *img, const psdr_grads *grads) {
+// The same sample loop for any sink; geo: the camera kernels with geometric adjoints (a triangle or camera table wanted)
+template <class Sink>
+int render_rev_host(const psdr_scene_desc *d, const psdr_render_opts *o, const float *adj, float *img, Sink &sink, bool geo) {
     HostScene hs;
     if (!setup(hs, d)) return 1;
     const int W = d->width, H = d->height;
     const long long WH = (long long) W * H;
     LiParams lp{o->integrator, o->bsdf_samples, o->light_samples, o->max_depth, o->hide_emitters, o->field};
-    HostSink sink; sink.g = *grads;
     TraversalStack st; uint32_t nr = 0;
     std::vector<double> acc((size_t) WH * 3, 0.0);
     const int nsp = o->spp_end - o->spp_begin;
@@ -262,7 +261,6 @@ extern "C" int hostcheck_render_rev(const psdr_scene_desc *d, const psdr_render_
             const float inv = 1.f / o->spp;
             const Vec3f a{adj[pixel * 3] * inv, adj[pixel * 3 + 1] * inv, adj[pixel * 3 + 2] * inv};
             PrimaryGrad pg; PathRec rec;
-            const bool geo = grads->g_tri_info != nullptr || grads->g_cam_to_world != nullptr;
             const Vec3f r = geo ? camera_sample_reverse<true>(sink, pg, rec, hs.sc, st, lp, jump, pixel, (uint64_t) pixel * o->spp + s, a, nr)
                                 : camera_sample_reverse<false>(sink, pg, rec, hs.sc, st, lp, jump, pixel, (uint64_t) pixel * o->spp + s, a, nr);
             if (pg.tri >= 0) for (int w = 0; w < kPrimaryWords; ++w) sink.add_tri(pg.tri, w, pg.w[w]);
@@ -286,4 +284,33 @@ extern "C" int hostcheck_render_rev(const psdr_scene_desc *d, const psdr_render_
     }
     if (img) for (size_t i = 0; i < acc.size(); ++i) img[i] = (float) acc[i];
     return 0;
+}
+
+// The reference of the GPU's scatter: every fp32 piece the estimators hand to the sink, summed in DOUBLE per entry, with the sum of the pieces'
+// magnitudes beside it (the scale against which an fp32 sum of that entry is judged: the pieces of one entry cancel).
+struct HostSinkF64 {
+    static constexpr int flags = kSceneAll;
+    static constexpr bool has_env = true;
+    double *sum[7], *abs[7];               // psdr_grads order: tri_info, texels, emitter_rad, cam_to_world, sec_edge, prim_edge, env_f
+    void put(int t, size_t i, float v) const { if (sum[t] && v != 0.f && std::isfinite(v)) { sum[t][i] += v; abs[t][i] += std::fabs((double) v); } }
+    void add_tri(int tri, int word, float v) const { put(0, (size_t) tri * PSDR_TRI_STRIDE + word, v); }
+    void add_texel(int idx, float v) const { put(1, idx, v); }
+    void add_rad(int e, int c, float v) const { put(2, (size_t) e * 3 + c, v); }
+    void add_cam(int w, float v) const { put(3, w, v); }
+    void add_sedge(int e, int w, float v) const { put(4, (size_t) e * PSDR_SEDGE_STRIDE + w, v); }
+    void add_pedge(int e, int w, float v) const { put(5, (size_t) e * PSDR_PEDGE_STRIDE + w, v); }
+    void add_env(int w, float v) const { put(6, w, v); }
+};
+}  // namespace
+
+extern "C" int hostcheck_render_rev(const psdr_scene_desc *d, const psdr_render_opts *o, const float *adj, float *img, const psdr_grads *grads) {
+    HostSink sink; sink.g = *grads;
+    return render_rev_host(d, o, adj, img, sink, grads->g_tri_info != nullptr || grads->g_cam_to_world != nullptr);
+}
+
+// sums[t] / abs_sums[t]: zeroed double buffers of the table's size, or null where the table is not wanted (t in psdr_grads order)
+extern "C" int hostcheck_render_rev_f64(const psdr_scene_desc *d, const psdr_render_opts *o, const float *adj, float *img, double *const *sums, double *const *abs_sums) {
+    HostSinkF64 sink;
+    for (int t = 0; t < 7; ++t) { sink.sum[t] = sums[t]; sink.abs[t] = sums[t] ? abs_sums[t] : nullptr; }
+    return render_rev_host(d, o, adj, img, sink, sums[0] != nullptr || sums[3] != nullptr);
 }

@@ -42,6 +42,8 @@ def test_version_and_error_strings_without_gpu():
     assert lib.psdr_scene_set_tables(None, None) != 0
     assert b"null" in lib.psdr_last_error()
     assert lib.psdr_render_c(None, None, None, None) != 0
+    out = (C.c_int32 * 16)()
+    assert lib.psdr_scene_rev_layout(None, out) != 0 and b"null" in lib.psdr_last_error()
 
 
 def test_product_package_never_imports_the_oracle():

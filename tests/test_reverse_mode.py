@@ -5,7 +5,7 @@ product code on the host (hostcheck) here and through the C ABI on the GPU (-m g
 import numpy as np
 import pytest
 
-from helpers import (GpuScene, dot_tables, host_render, host_render_rev, load_scene, random_tangents, rel_l2, same_rays)
+from helpers import (GpuScene, dot_tables, entry_errors, host_render, host_render_rev, host_render_rev_f64, load_scene, random_tangents, rel_l2, same_rays)
 from psdr_cuda import _abi
 
 CASES = [
@@ -56,6 +56,27 @@ def test_dot_product_identity_host(scene, kw, names, sppe, sppse):
         scale = float(np.abs(adj.astype(np.float64) * dimg).sum())       # the sum itself may cancel
         assert abs(lhs - rhs) <= 1e-4 * max(scale, 1e-6), (n, lhs, rhs, scale)
         assert rel_l2(img_r, img_f) < 1e-4          # the reverse pass also delivers the primal image
+
+
+@pytest.mark.parametrize("scene,kw,names,sppe,sppse", CASES)
+def test_host_sink_matches_the_f64_reference_per_entry(scene, kw, names, sppe, sppse):
+    """The double-precision reference of the scatter (hostcheck_render_rev_f64: the same estimator calls, every gradient entry summed in double with the
+    sum of its pieces' magnitudes beside it) against the fp32 host sink, ENTRY BY ENTRY: an fp32 running sum of pieces whose magnitudes add up to S is
+    off by a few eps32 S.  What the GPU tests (tests/test_gradient_sink_gpu.py) judge every cache arm by is therefore what it claims to be."""
+    tb, o, adj = _setup(scene, kw, sppe, sppse)
+    img32, g32 = host_render_rev(tb, o, adj, want=names)
+    img64, g64 = host_render_rev_f64(tb, o, adj, want=names)
+    assert np.array_equal(img32, img64)                  # the same samples
+    for n in names:
+        s, sa = g64[n]
+        assert g32[n].shape == s.shape, n
+        if n != "sec_edge":                              # (cbox_env: no secondary-edge sample lands on an edge at 16^2 x 4)
+            assert sa.max() > 0, n
+        assert (g32[n][sa == 0] == 0).all() and (s[sa == 0] == 0).all(), n      # an entry no piece reached is exactly zero in both
+        assert (np.abs(s) <= sa * (1 + 1e-12)).all(), n
+        # measured on these cases: |fp32 - f64| <= 11.3 eps32 abs_sum (cbox_rough light_samples=2, texels); sequential fp32 sums of up to thousands of pieces
+        worst, bad = entry_errors(g32[n], g64[n], 32.0, 0.0)
+        assert not bad.any(), (n, worst, int(bad.sum()))
 
 
 def test_reverse_gradient_equals_forward_columns():
