@@ -304,6 +304,23 @@ int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *opts,
                      const int32_t reso[4], int32_t nrounds,
                      float *out_mass, void *stream);
 
+/* Replaces HyperCubeDistribution<ndim>::sample_reuse (src/core/cube_distrb.cpp:41-48), ndim = 2 or 3:
+   samples [m][ndim] are warped IN PLACE, out_pdf [m] = pmf * n.  cmf / pmf / sum as DiscreteDistribution
+   holds them (src/core/pmf.cpp:7-14: inclusive prefix sum, unnormalised), reso [ndim], n = prod(reso).
+   A one-cell grid leaves the samples as they are with pdf 1, whatever its mass (DiscreteDistribution's
+   size-1 shortcut); on more cells an all-zero mass (sum = 0) gives pdf 0 (the reference: 0 / 0). */
+int psdr_cube_sample_reuse(int32_t ndim, const int32_t *reso, const float *cmf, const float *pmf, float sum,
+                           int32_t n, int32_t m, float *samples, float *out_pdf, void *stream);
+/* Replaces Scene::sample_boundary_segment_direct (src/scene/scene.cpp:456-492) over the tables of a
+   scene descriptor -- the one psdr_scene_set_tables takes; no handle, no tree: sample3 [m][3], active [m]
+   (NULL = all).  out_p0, out_edge_dir, out_edge2, out_p2, out_n [m][3]; out_pdf [m] (0 where invalid),
+   out_valid [m]; out_edge [m] = the secondary-edge row drawn, out_s1 [m] = the sample reused along it.
+   Every emitter kind is sampled as the render kernels do (scene.cpp:427-447). */
+int psdr_sample_boundary_segment_direct(const psdr_scene_desc *desc, int32_t m, const float *sample3,
+                                        const uint8_t *active, float *out_p0, float *out_edge_dir,
+                                        float *out_edge2, float *out_p2, float *out_n, float *out_pdf,
+                                        uint8_t *out_valid, int32_t *out_edge, float *out_s1, void *stream);
+
 /* ---- the differentiable table chain of Scene::configure as kernels (csrc/psdr_tables.hip) -------------------------------------
    All pointers are device pointers; vertices [V][3], faces [T][3] int32 (global vertex ids), rows [T][row_stride >= 22] in the
    TriangleInfo layout (PSDR_TRI_STRIDE words when written straight into tri_info), edges [E][5] int32 = v0, v1, face0, face1

@@ -1121,16 +1121,35 @@ template <class G, class M> struct Bsdf {
 // -------------------------------------------------------------------------- emitters
 template <class R> struct PosSample { Vec3<R> p, n; R J; float pdf; bool valid; int tri; };          // tri: the emitter triangle the point lies on (-1: the environment map)
 
+// HyperCubeDistribution<NDIM>::sample_reuse (src/core/cube_distrb.cpp:41-48), NDIM = 2 or 3: the cell is drawn on the last coordinate
+// (DiscreteDistribution::sample_reuse over n = r0 * r1 (* r2) cells), the sample is moved into it; returns pmf * n.  Cell (c0, c1, c2) has index
+// (c0 * r1 + c1) * r2 + c2 (cube_distrb.cpp:19-26).  Shared by the env-map cells, the guiding grid and k_cube_sample_reuse (psdr_hip.hip).
+template <int NDIM>
+PSDR_HD float cube_sample_reuse(const float *__restrict__ cmf, const float *__restrict__ pmf, float sum, int n, int r0, int r1, int r2, float s[NDIM]) {
+    static_assert(NDIM == 2 || NDIM == 3, "cube_sample_reuse: 2 or 3 dimensions");
+    float p;
+    const int idx = sample_reuse(cmf, pmf, sum, n, s[NDIM - 1], p);
+    if constexpr (NDIM == 2) {
+        const int c0 = idx / r1, c1 = idx - c0 * r1;
+        s[0] = (s[0] + (float) c0) * (1.f / (float) r0);
+        s[1] = (s[1] + (float) c1) * (1.f / (float) r1);
+    } else {
+        const int c0 = idx / (r1 * r2), rem = idx - c0 * r1 * r2, c1 = rem / r2, c2 = rem - c1 * r2;
+        s[0] = (s[0] + (float) c0) * (1.f / (float) r0);
+        s[1] = (s[1] + (float) c1) * (1.f / (float) r1);
+        s[2] = (s[2] + (float) c2) * (1.f / (float) r2);
+    }
+    return p * (float) n;
+}
+
 // HyperCubeDistribution<2>::sample_reuse / pdf (src/core/cube_distrb.cpp:42-62) of the env-map cells;
 // cell (x, y) has index x * reso[1] + y (cube_distrb.cpp:19-26)
 PSDR_HD float env_cells_sample_reuse(const SceneView &sc, float &u0, float &u1) {
-    const int r0 = sc.d.env_reso[0], r1 = sc.d.env_reso[1], n = r0 * r1;
-    float pmf;
-    const int idx = sample_reuse(sc.d.env_cmf, sc.d.env_pmf, sc.d.env_sum, n, u1, pmf);
-    const int c0 = idx / r1, c1 = idx - c0 * r1;
-    u0 = (u0 + (float) c0) * (1.f / (float) r0);
-    u1 = (u1 + (float) c1) * (1.f / (float) r1);
-    return pmf * (float) n;
+    const int r0 = sc.d.env_reso[0], r1 = sc.d.env_reso[1];
+    float s[2] = {u0, u1};
+    const float pdf = cube_sample_reuse<2>(sc.d.env_cmf, sc.d.env_pmf, sc.d.env_sum, r0 * r1, r0, r1, 1, s);
+    u0 = s[0]; u1 = s[1];
+    return pdf;
 }
 PSDR_HD float env_cells_pdf(const SceneView &sc, float u0, float u1) {
     const int r0 = sc.d.env_reso[0], r1 = sc.d.env_reso[1];
@@ -1754,32 +1773,32 @@ PSDR_HD double camera_return_distance(const SceneView &sc, int tri_c, float hu, 
 
 // HyperCubeDistribution<3>::sample_reuse (src/core/cube_distrb.cpp:41-48)
 PSDR_HD float guide_sample_reuse(const SceneView &sc, float s[3]) {
-    float pmf;
-    const int n = sc.d.num_guide_cells;
-    const int idx = sample_reuse(sc.d.guide_cmf, sc.d.guide_pmf, sc.d.guide_sum, n, s[2], pmf);
-    const int r1 = sc.d.guide_reso[1], r2 = sc.d.guide_reso[2];
-    const int c0 = idx / (r1 * r2), rem = idx - c0 * r1 * r2, c1 = rem / r2, c2 = rem - c1 * r2;
-    s[0] = (s[0] + (float) c0) * (1.f / (float) sc.d.guide_reso[0]);
-    s[1] = (s[1] + (float) c1) * (1.f / (float) r1);
-    s[2] = (s[2] + (float) c2) * (1.f / (float) r2);
-    return pmf * (float) n;
+    return cube_sample_reuse<3>(sc.d.guide_cmf, sc.d.guide_pmf, sc.d.guide_sum, sc.d.num_guide_cells, sc.d.guide_reso[0], sc.d.guide_reso[1],
+                                sc.d.guide_reso[2], s);
 }
 
 // DirectIntegrator::eval_secondary_edge (direct.cpp:225-316) + Scene::sample_boundary_segment_direct
 // (scene.cpp:456-492).  R = float: returns value0 (guiding, pixel -1); R = Dual<K>: tangent-only value.
-// What decides whether a secondary-edge slot evaluates anything at all (sample_boundary_segment_direct + the first two rays of
-// eval_secondary_edge, direct.cpp:225-262): the boundary segment must reach the emitter sample from the edge point and continue
-// backwards onto a surface.  A few per cent of the slots pass.  The same draws and the same float arithmetic as
-// secondary_edge_sample / secondary_edge_reverse, which repeat it for the survivors of a split launch (k_secondary_edge_filter).
+// Scene::sample_boundary_segment_direct (scene.cpp:456-492): the edge draw, p0 / edge / edge2, the emitter sample and the validity test of
+// cosTheta and the EdgeEpsilon sign tests -- no ray.  secondary_edge_survives (the filter of a split launch) and k_boundary_segment_direct
+// (psdr_hip.hip, the C ABI) call it, so a user's draw is the renderer's draw; what a caller does not read (edge, pdf) is dead code after
+// inlining (the filter kernels disassemble to the same code as before).  Two copies remain, to be kept in step with this one: secondary_edge_rays
+// (sharing moved the probe kernel's code, see there) and secondary_edge_sample, which loads p0 and e1 as dual numbers for forward mode.
+// A draw that lands on a dropped row of a capacity table (all zero, pmf 0) fails the sign tests.
+struct BoundarySeg { Vec3f p0, edge, edge2, p2, n; float pdf, s1; int k; bool valid; };
 template <int FL>
-PSDR_HD bool secondary_edge_survives(const SceneView &sc, TraversalStack &st, const float s3[3], uint32_t &nrays) {
+PSDR_HD BoundarySeg boundary_segment_direct(const SceneView &sc, const float s3[3]) {
     const TangentView<0, FL> tv0{};
+    BoundarySeg r;
     float s1 = s3[0], pdf0;
     const int k = sample_reuse(sc.d.sec_cmf, sc.d.sec_pmf, sc.d.sec_sum, sc.d.num_sec_edges, s1, pdf0);
     const float *se = sc.d.sec_edge + (size_t) k * PSDR_SEDGE_STRIDE;
-    const Vec3f ep0{se[0], se[1], se[2]}, ee1{se[3], se[4], se[5]}, n0{se[6], se[7], se[8]}, n1{se[9], se[10], se[11]};
+    const Vec3f ep0{se[0], se[1], se[2]}, ee1{se[3], se[4], se[5]}, n0{se[6], se[7], se[8]}, n1{se[9], se[10], se[11]}, ep2{se[12], se[13], se[14]};
     const bool is_boundary = se[15] != 0.f;
     const Vec3f p0 = ee1 * s1 + ep0;
+    const float e1len = norm(ee1);
+    r.p0 = p0; r.edge = ee1 / e1len; r.edge2 = ep2 - ep0; r.s1 = s1; r.k = k;
+    pdf0 /= e1len;
     const PosSample<float> ps2 = sample_emitter_position<float>(sc, tv0, p0, s3[1], s3[2], false);
     const Vec3f p2 = ps2.p, bn = ps2.n;
     Vec3f e = p2 - p0;
@@ -1788,7 +1807,23 @@ PSDR_HD bool secondary_edge_survives(const SceneView &sc, TraversalStack &st, co
     const float cosTheta = -dot(bn, e);
     const float d0n = dot(n0, e), d1n = dot(n1, e);
     const int sgn0 = d0n > kEdgeEpsilon ? 1 : (d0n < -kEdgeEpsilon ? -1 : 0), sgn1 = d1n > kEdgeEpsilon ? 1 : (d1n < -kEdgeEpsilon ? -1 : 0);
-    bool valid = cosTheta > kEpsilon && (is_boundary ? sgn0 != 0 : sgn0 * sgn1 < 0);
+    r.valid = cosTheta > kEpsilon && (is_boundary ? sgn0 != 0 : sgn0 * sgn1 < 0);
+    r.pdf = r.valid ? pdf0 * ps2.pdf * (distSqr / cosTheta) : 0.f;
+    r.p2 = p2; r.n = bn;
+    return r;
+}
+
+// What decides whether a secondary-edge slot evaluates anything at all (sample_boundary_segment_direct + the first two rays of
+// eval_secondary_edge, direct.cpp:225-262): the boundary segment must reach the emitter sample from the edge point and continue
+// backwards onto a surface.  A few per cent of the slots pass.  The same draws and the same float arithmetic as
+// secondary_edge_sample / secondary_edge_reverse, which repeat it for the survivors of a split launch (k_secondary_edge_filter).
+template <int FL>
+PSDR_HD bool secondary_edge_survives(const SceneView &sc, TraversalStack &st, const float s3[3], uint32_t &nrays) {
+    const TangentView<0, FL> tv0{};
+    const BoundarySeg bs = boundary_segment_direct<FL>(sc, s3);
+    const Vec3f p0 = bs.p0, p2 = bs.p2;
+    const int k = bs.k;
+    bool valid = bs.valid;
     const Vec3f dir = normalize(p2 - p0);
     const bool skip = sc.d.sec_edge_faces != nullptr && !sc.literal_forms;
     const int f0 = skip ? sc.d.sec_edge_faces[2 * k] : -1, f1 = skip ? sc.d.sec_edge_faces[2 * k + 1] : -1;
@@ -1800,7 +1835,8 @@ PSDR_HD bool secondary_edge_survives(const SceneView &sc, TraversalStack &st, co
 
 // What the dense trace kernel needs of a secondary-edge slot BEFORE that test (the probe pass of a traced launch, psdr_kernels.h k_se_probe): the
 // geometric part of the decision, the edge point, the direction towards the emitter sample and the edge (its adjacent faces are skipped by
-// both rays).  The same draws and the same arithmetic as secondary_edge_survives.
+// both rays).  The same draws and the same arithmetic as boundary_segment_direct, written out: built on it, k_se_probe<4> compiled to other
+// code (2633 -> 2608 instructions), and the render kernels stay as they were -- keep the two in step.
 template <int FL>
 PSDR_HD bool secondary_edge_rays(const SceneView &sc, const float s3[3], Vec3f &p0, Vec3f &dir, int &edge) {
     const TangentView<0, FL> tv0{};

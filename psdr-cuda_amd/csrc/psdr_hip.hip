@@ -391,6 +391,48 @@ __global__ __launch_bounds__(kBlock) void k_primary_edge_keys(SceneView sc, RngJ
     vals[j] = (uint32_t) j;
 }
 
+// ------------------------------------------------------------------ sampling on the Python surface
+// HyperCubeDistribution{2,3}f.sample_reuse (psdr_cube_sample_reuse): one lane per sample, the sample warped in place.  The tables stay in global
+// memory: a grid of a million cells is 8 MB, L2 / MALL resident; what a lane waits for is the chain of dependent loads of the binary search,
+// and without LDS the kernel keeps the full complement of waves in flight to cover it.
+template <int NDIM>
+__global__ __launch_bounds__(kBlock) void k_cube_sample_reuse(int m, const float *__restrict__ cmf, const float *__restrict__ pmf, float sum, int n,
+                                                              int r0, int r1, int r2, float *__restrict__ samples, float *__restrict__ out_pdf) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    float s[NDIM];
+#pragma unroll
+    for (int d = 0; d < NDIM; ++d) s[d] = samples[(size_t) i * NDIM + d];
+    const float pdf = cube_sample_reuse<NDIM>(cmf, pmf, sum, n, r0, r1, r2, s);
+#pragma unroll
+    for (int d = 0; d < NDIM; ++d) samples[(size_t) i * NDIM + d] = s[d];
+    out_pdf[i] = (n == 1 || sum > 0.f) ? pdf : 0.f;    // all-zero mass: pdf 0 (the reference's 0 / 0); one cell: pdf 1 whatever its mass
+}
+
+// Scene.sample_boundary_segment_direct (psdr_sample_boundary_segment_direct): one lane per sample, boundary_segment_direct of the render
+// kernels' flag set with (FL = kSceneEnv) or without an environment map.  No ray, no tree: every table is read from global memory.
+template <int FL>
+__global__ __launch_bounds__(kBlock) void k_boundary_segment_direct(SceneView sc, int m, const float *__restrict__ sample3, const uint8_t *__restrict__ active,
+                                                                    float *__restrict__ out_p0, float *__restrict__ out_edge_dir, float *__restrict__ out_edge2,
+                                                                    float *__restrict__ out_p2, float *__restrict__ out_n, float *__restrict__ out_pdf,
+                                                                    uint8_t *__restrict__ out_valid, int32_t *__restrict__ out_edge, float *__restrict__ out_s1) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    const float s3[3] = {sample3[3 * (size_t) i], sample3[3 * (size_t) i + 1], sample3[3 * (size_t) i + 2]};
+    const BoundarySeg r = boundary_segment_direct<FL>(sc, s3);
+    const bool valid = r.valid && (active == nullptr || active[i] != 0);
+    const size_t o = 3 * (size_t) i;
+    out_p0[o] = r.p0.x; out_p0[o + 1] = r.p0.y; out_p0[o + 2] = r.p0.z;
+    out_edge_dir[o] = r.edge.x; out_edge_dir[o + 1] = r.edge.y; out_edge_dir[o + 2] = r.edge.z;
+    out_edge2[o] = r.edge2.x; out_edge2[o + 1] = r.edge2.y; out_edge2[o + 2] = r.edge2.z;
+    out_p2[o] = r.p2.x; out_p2[o + 1] = r.p2.y; out_p2[o + 2] = r.p2.z;
+    out_n[o] = r.n.x; out_n[o + 1] = r.n.y; out_n[o + 2] = r.n.z;
+    out_pdf[i] = valid ? r.pdf : 0.f;
+    out_valid[i] = valid ? 1 : 0;
+    out_edge[i] = r.k;
+    out_s1[i] = r.s1;
+}
+
 #include "psdr_lbvh.h"
 __global__ void k_scatter_hot(int32_t *__restrict__ map, const int32_t *__restrict__ tris, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1401,6 +1443,59 @@ int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *o, const int32_t re
     if (n <= 0 || n > 0x7fffffffLL) return fail("psdr_guide_build: invalid resolution");
     HIP_TRY(hipMemsetAsync(out_mass, 0, sizeof(float) * cells, s));
     return variant_of(h)->guide(h, cx, reso, nrounds, n, out_mass, s);
+}
+
+int psdr_cube_sample_reuse(int32_t ndim, const int32_t *reso, const float *cmf, const float *pmf, float sum, int32_t n, int32_t m, float *samples,
+                           float *out_pdf, void *stream) {
+    if (!reso || !cmf || !pmf || !samples || !out_pdf) return fail("psdr_cube_sample_reuse: null argument");
+    if (ndim != 2 && ndim != 3) return fail("psdr_cube_sample_reuse: ndim must be 2 or 3");
+    long long cells = 1;
+    for (int d = 0; d < ndim; ++d) {
+        if (reso[d] <= 0) return fail("psdr_cube_sample_reuse: invalid resolution");
+        cells *= reso[d];
+    }
+    if (cells != (long long) n) return fail("psdr_cube_sample_reuse: n must be the product of the resolution");
+    if (m < 0) return fail("psdr_cube_sample_reuse: negative sample count");
+    if (m == 0) return 0;
+    const dim3 grid((unsigned) ((m + kBlock - 1) / kBlock));
+    hipStream_t s = (hipStream_t) stream;
+    if (ndim == 2)
+        hipLaunchKernelGGL(k_cube_sample_reuse<2>, grid, dim3(kBlock), 0, s, m, cmf, pmf, sum, n, reso[0], reso[1], 1, samples, out_pdf);
+    else
+        hipLaunchKernelGGL(k_cube_sample_reuse<3>, grid, dim3(kBlock), 0, s, m, cmf, pmf, sum, n, reso[0], reso[1], reso[2], samples, out_pdf);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int psdr_sample_boundary_segment_direct(const psdr_scene_desc *desc, int32_t m, const float *sample3, const uint8_t *active, float *out_p0,
+                                        float *out_edge_dir, float *out_edge2, float *out_p2, float *out_n, float *out_pdf, uint8_t *out_valid,
+                                        int32_t *out_edge, float *out_s1, void *stream) {
+    if (!desc || !sample3 || !out_p0 || !out_edge_dir || !out_edge2 || !out_p2 || !out_n || !out_pdf || !out_valid || !out_edge || !out_s1)
+        return fail("psdr_sample_boundary_segment_direct: null argument");
+    const psdr_scene_desc &d = *desc;
+    if (d.num_sec_edges <= 0 || !d.sec_edge || !d.sec_cmf || !d.sec_pmf) return fail("Scene has no secondary edges");
+    if (d.num_emitters <= 0 || !d.emitter_f || !d.emitter_i) return fail("No Emitter!");
+    if (d.num_emitters > 1 && (!d.emitter_cmf || !d.emitter_pmf)) return fail("psdr_sample_boundary_segment_direct: emitter distribution missing");
+    const bool env = d.env_f != nullptr && d.env_emitter >= 0;
+    if (env && (d.env_emitter >= d.num_emitters || !d.env_cmf || !d.env_pmf || d.env_reso[0] <= 0 || d.env_reso[1] <= 0))
+        return fail("psdr_sample_boundary_segment_direct: inconsistent environment-map record");
+    if (d.num_emitters > (env ? 1 : 0) && (d.num_tris <= 0 || !d.tri_info || !d.face_cmf || !d.face_pmf))
+        return fail("psdr_sample_boundary_segment_direct: area-light tables missing");
+    if (m < 0) return fail("psdr_sample_boundary_segment_direct: negative sample count");
+    if (m == 0) return 0;
+    SceneView sc{};
+    sc.d = d;
+    if (!env) sc.d.env_emitter = -1;
+    const dim3 grid((unsigned) ((m + kBlock - 1) / kBlock));
+    hipStream_t s = (hipStream_t) stream;
+    if (env)
+        hipLaunchKernelGGL(k_boundary_segment_direct<kSceneEnv>, grid, dim3(kBlock), 0, s, sc, m, sample3, active, out_p0, out_edge_dir, out_edge2, out_p2, out_n,
+                           out_pdf, out_valid, out_edge, out_s1);
+    else
+        hipLaunchKernelGGL(k_boundary_segment_direct<0>, grid, dim3(kBlock), 0, s, sc, m, sample3, active, out_p0, out_edge_dir, out_edge2, out_p2, out_n,
+                           out_pdf, out_valid, out_edge, out_s1);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int psdr_bvh_stats(psdr_scene_t h, int32_t out[4]) {

@@ -88,6 +88,7 @@ HIP_SYMBOLS = (
     "psdr_geo_world_vertices_fwd", "psdr_geo_world_vertices_rev", "psdr_geo_tri_rows_fwd", "psdr_geo_tri_rows_rev", "psdr_geo_sec_edges_fwd", "psdr_geo_sec_edges_rev", "psdr_geo_prim_edges_fwd", "psdr_geo_prim_edges_rev",
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
     "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
+    "psdr_cube_sample_reuse", "psdr_sample_boundary_segment_direct",
 )
 
 HIP_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libpsdr_hip.so")   # the in-tree build; the package reads NO environment variable
@@ -146,6 +147,8 @@ def load_hip():
     lib.psdr_geo_prim_edges_jvp.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
     lib.psdr_geo_compact_edges_jvp.argtypes = [i32, i32, vp, vp, vp, vp]
     lib.psdr_geo_emitter_tables.argtypes = [i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.psdr_cube_sample_reuse.argtypes = [i32, C.POINTER(i32), vp, vp, C.c_float, i32, i32, vp, vp, vp]
+    lib.psdr_sample_boundary_segment_direct.argtypes = [C.POINTER(SceneDesc), i32] + [vp] * 12
     for name in HIP_SYMBOLS:
         if name not in ("psdr_last_error", "psdr_version"):
             getattr(lib, name).restype = C.c_int

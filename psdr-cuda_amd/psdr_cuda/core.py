@@ -1,4 +1,6 @@
 """Small host-side value types of the psdr_cuda surface (reference src/psdr.cpp:48-178)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -337,6 +339,58 @@ class HyperCubeDistribution3f:
         idx = idx.clamp(0, self.m_num_cells - 1)
         val = self.m_distrb.m_pmf[idx] / self.m_distrb.m_sum * self.m_num_cells
         return FloatC(torch.where(valid, val, torch.zeros_like(val)))
+
+
+    def sample_reuse(self, samples):
+        """HyperCubeDistribution<ndim>::sample_reuse (cube_distrb.cpp:41-48): the cell is drawn on the last coordinate and `samples` -- a
+        Vector{2,3}fC or an [m, ndim] tensor -- is warped into it IN PLACE; returns the pdf (pmf * number of cells) as a FloatC.
+        Device samples run k_cube_sample_reuse (csrc/psdr_hip.hip, the decode the render kernels use for the guiding grid and the
+        env-map cells); CPU samples the same arithmetic in torch.  A one-cell grid leaves the samples as they are, pdf 1.  An all-zero
+        mass moves every sample into cell 0 with pdf 0 (the reference divides 0 by 0 there)."""
+        psdr_assert(self.m_ready)
+        t = samples.t if isinstance(samples, ek.ArrayBase) else samples
+        psdr_assert(isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == self.ndim,
+                    "sample_reuse: expected [m, %d] samples" % self.ndim)
+        m = int(t.shape[0])
+        if self.m_num_cells == 1:
+            return FloatC._wrap(torch.ones(m, dtype=torch.float32, device=t.device))
+        dd = self.m_distrb
+        total = dd.m_sum
+        inplace = t.dtype == torch.float32 and t.is_contiguous()
+        work = t.detach() if inplace else t.detach().to(torch.float32).contiguous()          # (detach: the caller's storage itself)
+        cmf, pmf = dd.m_cmf.to(t.device), dd.m_pmf.to(t.device)
+        if t.is_cuda:
+            from . import _abi
+            lib = _abi.load_hip()
+            pdf = torch.empty(m, dtype=torch.float32, device=t.device)
+            if m > 0:
+                reso = (ctypes.c_int32 * self.ndim)(*self.m_resolution)
+                _abi.check(lib, lib.psdr_cube_sample_reuse(self.ndim, reso, cmf.data_ptr(), pmf.data_ptr(), total, self.m_num_cells, m,
+                                                           work.data_ptr(), pdf.data_ptr(),
+                                                           ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)))
+        else:
+            pdf = _cube_sample_reuse_torch(cmf, pmf, total, self.m_resolution, work)
+        if not inplace:
+            with torch.no_grad():
+                t.copy_(work)
+        return FloatC._wrap(pdf)
+
+
+def _cube_sample_reuse_torch(cmf, pmf, total, reso, s):
+    """k_cube_sample_reuse in torch (host path of HyperCubeDistribution.sample_reuse): DiscreteDistribution::sample_reuse on the last column,
+    then the cell decode; s [m, ndim] float32 is written in place, returns the pdf."""
+    n = int(cmf.shape[0])
+    u = s[:, -1] * total
+    idx = torch.searchsorted(cmf, u.contiguous(), right=False).clamp(max=n - 1)
+    u = u - torch.where(idx > 0, cmf[(idx - 1).clamp(min=0)], torch.zeros_like(u))
+    p = pmf[idx]
+    s[:, -1] = torch.where(p > 0, u / p, u).clamp(0.0, 1.0)
+    pdf = p / total * n if total > 0 else torch.zeros_like(u)
+    for d in range(len(reso) - 1, -1, -1):
+        c = idx % reso[d]
+        idx = idx // reso[d]
+        s[:, d] = (s[:, d] + c.to(torch.float32)) * (1.0 / reso[d])
+    return pdf
 
 
 class HyperCubeDistribution2f(HyperCubeDistribution3f):

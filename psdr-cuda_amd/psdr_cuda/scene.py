@@ -6,6 +6,7 @@ records, camera matrices, distributions) is done here with torch ops on the rend
 chain  user parameters -> tables  stays differentiable by torch autograd, while the O(W*H*spp)
 work is done by the hand-written HIP kernels behind include/psdr_hip.h.
 """
+import ctypes as C
 import math
 import os
 import time
@@ -441,6 +442,25 @@ class PerspectiveCamera(Sensor):
 PositionSample = PositionSampleD      # kept as an alias (older name of this build)
 
 
+class _TensorNode:
+    """The forward-mode node of a differentiable array computed in torch (Scene.sample_boundary_segment_direct's p0): enoki.forward(P)
+    gives it d tensor / d P (enoki/_array.py forward).  release() (enoki.forward with free_graph) drops the graph and keeps the shape: a later
+    enoki.forward finds no path to its parameter and returns zeros, as for an array whose graph Enoki has freed."""
+
+    def __init__(self, t):
+        self._t = t
+        self._shape, self._dtype, self._device = t.shape, t.dtype, t.device
+
+    def input_tensors(self):
+        return [self._t]
+
+    def render_forward(self, tangents):
+        return tangents[0] if tangents[0] is not None else torch.zeros(self._shape, dtype=self._dtype, device=self._device)
+
+    def release(self):
+        self._t = None
+
+
 class BoundarySegSampleDirect:
     """records.h:35-44: pdf, is_valid, p0 (differentiable), edge, edge2, p2, n."""
     pdf = is_valid = p0 = edge = edge2 = p2 = n = None
@@ -691,6 +711,16 @@ class Mesh(Object):
         self._vertex_offset = t
         self.m_ready = False
 
+    def shift_vertices(self):
+        """Mesh::shift_vertices (mesh.cpp:345-351): folds the vertex offset into the raw positions, raw <- raw + detach(n_raw) * detach(offset),
+        with n_raw the vertex normals of the current raw positions (what _raw_positions uses), and resets the offset to zeros -- a stored
+        tensor, so an optimisation loop can go on marking it as a parameter.  New tensors, not in-place updates: the configure cache sees them."""
+        if self._vertex_offset is not None:
+            _, n_raw = process_mesh(self._vertex_positions_raw.detach(), self._face_indices)
+            self._vertex_positions_raw = self._vertex_positions_raw + (n_raw * self._vertex_offset.unsqueeze(-1)).detach()
+        self._vertex_offset = torch.zeros(self.num_vertices, dtype=torch.float32, device=self._vertex_positions_raw.device)
+        self.m_ready = False
+
     def _raw_positions(self):
         """Object-space positions the transform is applied to (mesh.cpp:226-232)."""
         if self._vertex_offset is None:
@@ -804,8 +834,8 @@ class Mesh(Object):
         return ps
 
     def dump(self, fname):
-        """OBJ writer, reference mesh.cpp:354-418 (raw vertices, 1-based faces)."""
-        v = self._vertex_positions_raw.detach().cpu().numpy()
+        """OBJ writer, reference mesh.cpp:354-418 (raw vertices moved by the vertex offset, 1-based faces)."""
+        v = self._raw_positions().detach().cpu().numpy()
         f = self._face_indices.cpu().numpy()
         with open(fname, "w") as o:
             for p in v:
@@ -1684,8 +1714,63 @@ class Scene(Object):
         return self._configured and all(m.m_ready for m in self.m_meshes)
 
     def sample_boundary_segment_direct(self, sample3, active=True):
-        """Scene::sample_boundary_segment_direct (scene.cpp:456-492), host/torch mirror for API parity
-        (the kernels run their own copy per sample, csrc/psdr_device.h secondary_edge_sample)."""
+        """Scene::sample_boundary_segment_direct (scene.cpp:456-492) -> BoundarySegSampleDirect.  With the scene's tables on the GPU this is
+        k_boundary_segment_direct (include/psdr_hip.h psdr_sample_boundary_segment_direct): the draw of the render kernels, for any number of
+        area lights and an environment map.  p0 carries the derivative of the secondary-edge rows (enoki.backward and enoki.forward); the
+        other fields are detached, as in the reference.  Tables on the host: the torch mirror (_sample_boundary_segment_direct_torch)."""
+        tb = self._tables
+        psdr_assert(tb is not None and tb["num_sec_edges"] > 0, "Scene has no secondary edges")
+        if tb["sec_edge"].is_cuda:
+            return self._sample_boundary_segment_direct_native(sample3, active)
+        return self._sample_boundary_segment_direct_torch(sample3, active)
+
+    def _sample_boundary_segment_direct_native(self, sample3, active=True):
+        s = (sample3.t if isinstance(sample3, ek.ArrayBase) else torch.as_tensor(sample3))
+        dev = self._tables["sec_edge"].device
+        s = s.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        m = int(s.shape[0])
+        act = None
+        if isinstance(active, (bool, np.bool_)):
+            if not active:
+                act = torch.zeros(m, dtype=torch.uint8, device=dev)
+        else:
+            a = active.t if isinstance(active, ek.ArrayBase) else torch.as_tensor(active)
+            act = a.detach().to(device=dev).reshape(-1).expand(m).to(torch.uint8).contiguous()
+        tb = self.tables(0, capacity=True)          # the tables the render calls pass: no read-back of the kept-edge count
+        desc, keep = make_desc(tb)
+        f3 = lambda: torch.empty(m, 3, dtype=torch.float32, device=dev)
+        p0, edge, edge2, p2, n = f3(), f3(), f3(), f3(), f3()
+        pdf = torch.empty(m, dtype=torch.float32, device=dev)
+        valid = torch.empty(m, dtype=torch.uint8, device=dev)
+        k = torch.empty(m, dtype=torch.int32, device=dev)
+        s1 = torch.empty(m, dtype=torch.float32, device=dev)
+        if m > 0:
+            lib = _abi.load_hip()
+            ptr = lambda x: None if x is None else x.data_ptr()
+            _abi.check(lib, lib.psdr_sample_boundary_segment_direct(C.byref(desc), m, s.data_ptr(), ptr(act), p0.data_ptr(), edge.data_ptr(),
+                                                                     edge2.data_ptr(), p2.data_ptr(), n.data_ptr(), pdf.data_ptr(), valid.data_ptr(),
+                                                                     k.data_ptr(), s1.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        del keep
+        r = BoundarySegSampleDirect()
+        rows = tb["sec_edge"]
+        if rows.requires_grad:
+            # the kernel's value, the derivative of p0 = e1 * s1 + p0_edge through the differentiable rows (no adjoint kernel)
+            row = rows.index_select(0, k.long())
+            p0_t = row[:, 3:6] * s1.unsqueeze(-1) + row[:, 0:3]
+            r.p0 = Vector3fD._wrap(p0 + (p0_t - p0_t.detach()))
+            ek.register_render_node(r.p0)
+            r.p0._node = _TensorNode(p0_t)
+        else:
+            r.p0 = Vector3fD._wrap(p0)
+        r.edge, r.edge2, r.p2, r.n = Vector3fC._wrap(edge), Vector3fC._wrap(edge2), Vector3fC._wrap(p2), Vector3fC._wrap(n)
+        r.pdf = FloatC._wrap(pdf)
+        r.is_valid = valid.bool()
+        r._edge_index, r._s1 = k, s1          # the secondary-edge row drawn and the sample reused along it (not in the reference's record)
+        return r
+
+    def _sample_boundary_segment_direct_torch(self, sample3, active=True):
+        """Scene::sample_boundary_segment_direct as a torch mirror: the host path, and what the GPU tests compare the kernel with.
+        One area light only (the emitter draw of the mirror is m_emitters[0]'s mesh)."""
         tb = self._tables
         psdr_assert(tb is not None and tb["num_sec_edges"] > 0, "Scene has no secondary edges")
         psdr_assert(len(self.m_emitters) == 1, "host mirror supports a single emitter")
@@ -1716,6 +1801,9 @@ class Scene(Object):
         sg = lambda v: (v > EdgeEpsilon).to(torch.int32) - (v < -EdgeEpsilon).to(torch.int32)
         is_b = row[:, 15].detach() != 0
         valid = (cos_t > Epsilon) & torch.where(is_b, sg(d0) != 0, sg(d0) * sg(d1) < 0)
+        if not (isinstance(active, (bool, np.bool_)) and active):
+            a = active.t if isinstance(active, ek.ArrayBase) else torch.as_tensor(active, device=valid.device)
+            valid = valid & a.to(device=valid.device, dtype=torch.bool).reshape(-1)
         r.is_valid = valid
         r.pdf = FloatC._wrap(torch.where(valid, pdf0 * ps.pdf.t * d2 / cos_t, torch.zeros_like(d2)))
         return r
