@@ -8,16 +8,19 @@ DROP-IN SURFACE:
     run_ad pass     P = FloatD(0); set_requires_gradient(P); reflectance.data = base + P; scene.configure()
                     imgD = integrator.renderD(scene); enoki.forward(P); d = enoki.gradient(imgD)
 Metric: Mpath-samples/s = camera sample slots of the two passes / wall seconds / 1e6 (2 * W * H * spp per step),
-scene tables resident in HBM, device-synchronised.  `value` is this surface-inclusive rate; the same work as bare
-C-ABI launches (psdr_render_c + psdr_render_d_fwd, no Python / torch table chain) is reported beside it as
-`kernel_only`, and the reverse-mode variant of the AD pass (loss.backward -> psdr_render_d_rev) as `reverse`.
+scene tables resident in HBM, device-synchronised.  `value` is this surface-inclusive rate.  A plain run sets up, warms
+up, times the steps, writes --dump-outputs and prints the headline; everything else it measures or checks runs after the
+timed steps with `--full` only: the same work as bare C-ABI launches (psdr_render_c + psdr_render_d_fwd, no Python /
+torch table chain) as `kernel_only`, the reverse-mode variant of the AD pass (loss.backward -> psdr_render_d_rev) in
+`surface`, the roofline's counter passes, the CPU baseline, the gradient check against the oracle, `tree_scenes` and
+`c4_strong`.
 
 Multi-GPU (`--gpus N` under torch.distributed.run): the spp of every pixel are sharded across the ranks (weak
 scaling: per-GPU spp fixed at 64, global spp = 64 * N) and the image / derivative-image buffers are summed with ONE
 RCCL all-reduce per render call.
 
-`--pmc-child` (internal): a short run of the kernel-only launches under `rocprofv3 --pmc`, spawned by the parent to
-MEASURE the VALU instruction count and the HBM traffic of the dominant kernel in this very run.
+`--pmc-child` (internal): a short run of the kernel-only launches under `rocprofv3 --pmc`, spawned by a `--full` parent
+to MEASURE the VALU instruction count and the HBM traffic of the dominant kernel in this very run.
 
 Prints ONE JSON line on rank 0.
 """
@@ -63,6 +66,9 @@ def parse():
                     help="c2 (default, the headline): cbox 512x512 spp 64 PER GPU, albedo derivative, weak scaling.  c4: cbox_bunny 1024x1024, "
                          "GLOBAL spp 512 sharded over the ranks (strong scaling), renderC + renderD + enoki.backward w.r.t. the bunny's vertex "
                          "positions and the albedo texels (gradient-buffer all-reduce)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the side blocks as well: surface reverse steps, kernel_only, the roofline's counter passes, cpu_baseline, "
+                         "grad_rel_l2, tree_scenes, c4_strong (c2); the wavefront traffic passes (c4).  Off: the run does only what the headline needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -671,7 +677,7 @@ def run_c4(args, world, rank, local_rank, dist, devices, rccl):
     T = int(sc.tables(0)["num_tris"])
     # the wavefront stages' stream traffic against the HBM roofline: measured on one GPU's share of the 8-GPU job (64 spp: the launch size at
     # which the library runs the class-binned wavefront), record size 44 + 12 K bytes + 3 (1 + K) accumulator words per live path and stage
-    wf = pmc_passes_c4(args, res, max(spp // 8, 1)) if (rank == 0 and not args.no_pmc) else None
+    wf = pmc_passes_c4(args, res, max(spp // 8, 1)) if (rank == 0 and args.full and not args.no_pmc) else None
     if dist and world > 1:
         dist.barrier()
     grad_words = T * 24 + int(sc.tables(0)["texels"].numel())
@@ -824,7 +830,7 @@ def main():
         force_collectives(True)
     args.local_rank = local_rank
     side = None
-    if dist and world > 1:
+    if dist and world > 1 and args.full:
         # host-side barrier (gloo): the other ranks wait here -- no spinning collective on their GPUs, no RCCL watchdog -- while rank 0 runs the counter
         # passes (child processes under rocprofv3) and the single-GPU side blocks
         from datetime import timedelta
@@ -840,7 +846,6 @@ def main():
         if dist:
             dist.destroy_process_group()
         return
-    from psdr_cuda import _abi
     w = Workload(args, world)
 
     if args.pmc_child:                      # counted launches only: 2 x (renderC, renderD K=1, reverse)
@@ -878,7 +883,30 @@ def main():
     local_slots = args.res * args.res * args.spp
     slots_per_pass = local_slots * world                             # whole job
     value = 2.0 * slots_per_pass * args.steps / dt / 1e6
+    line = {
+        "metric": "Mpath-samples/s renderC+renderD, cbox 512x512 spp=64; grad rel-L2 vs ref",
+        "value": round(value, 3), "unit": "Mpath-samples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%s %dx%d spp=%d/GPU PathTracer(max_depth=%d): renderC + configure + renderD + enoki.forward w.r.t. diffuse albedo, through the psdr_cuda surface"
+                               % (args.scene, args.res, args.res, args.spp, args.max_depth),
+                   "triangles": int(w.sc.tables(0, capacity=True)["num_tris"]), "global_spp": args.spp * world, "world_size": world,
+                   "device": torch.cuda.get_device_name(local_rank), "local_rank": local_rank, "devices": devices, "rccl_version": rccl,
+                   "allreduce_bytes_per_step": 0 if world == 1 else int(args.res * args.res * 3 * 4 * 3),
+                   "parallelism": "spp-shard x%d, one all-reduce per render call ([image] for renderC, [image || derivative image] for renderD)" % world},
+    }
+    if args.full:
+        line.update(full_blocks(args, w, world, rank, dist, rccl, wait_all, dt, local_slots, slots_per_pass))
+    if rank == 0:
+        print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
 
+
+def full_blocks(args, w, world, rank, dist, rccl, wait_all, dt, local_slots, slots_per_pass):
+    """--full: what the run reports beside the headline, after its timed steps -- every rank takes part (rank 0 alone runs the single-GPU blocks
+    while the others wait at wait_all()); rank 0's dict is added to the result line."""
+    from psdr_cuda import _abi
     # ---- beside it: the surface with reverse mode, the bare kernels (HIP events on the launch stream), host shares
     n_side = max(5, min(20, args.steps))
     ms_rev_surface = timed(w.surface_reverse_step, n_side)
@@ -1047,24 +1075,8 @@ def main():
         except Exception as e:
             strong_one = {"error": repr(e)}
             wait_all()
-    if rank == 0:
-        out = {
-            "metric": "Mpath-samples/s renderC+renderD, cbox 512x512 spp=64; grad rel-L2 vs ref",
-            "value": round(value, 3), "unit": "Mpath-samples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s %dx%d spp=%d/GPU PathTracer(max_depth=%d): renderC + configure + renderD + enoki.forward w.r.t. diffuse albedo, through the psdr_cuda surface"
-                                   % (args.scene, args.res, args.res, args.spp, args.max_depth),
-                       "triangles": int(w.tb["num_tris"]), "global_spp": args.spp * world, "world_size": world,
-                       "device": torch.cuda.get_device_name(local_rank), "local_rank": local_rank, "devices": devices, "rccl_version": rccl,
-                       "allreduce_bytes_per_step": 0 if world == 1 else int(args.res * args.res * 3 * 4 * 3),
-                       "parallelism": "spp-shard x%d, one all-reduce per render call ([image] for renderC, [image || derivative image] for renderD)" % world},
-            "surface": surface, "kernel_only": kernel_only,
-            "roofline": roofline, "cpu_baseline": cpu, "grad_rel_l2": grad, "tree_scenes": trees, "c4_strong": strong, "c4_strong_one_integrator": strong_one,
-        }
-        print(json.dumps(out))
-    if dist:
-        dist.destroy_process_group()
+    return {"surface": surface, "kernel_only": kernel_only, "roofline": roofline, "cpu_baseline": cpu, "grad_rel_l2": grad, "tree_scenes": trees,
+            "c4_strong": strong, "c4_strong_one_integrator": strong_one}
 
 
 if __name__ == "__main__":

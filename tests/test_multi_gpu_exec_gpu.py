@@ -198,8 +198,8 @@ def test_bench_at_five_ranks_on_one_gpu(tmp_path):
     import json
     world = 5
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PSDR_BENCH_ONE_GPU="1")
-    codes, stdout, stderr = run_ranks(world, [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-pmc", "--no-cpu-baseline",
-                                              "--no-tree-scenes"], env, tmp_path, timeout=1800)
+    codes, stdout, stderr = run_ranks(world, [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--full", "--no-pmc",
+                                              "--no-cpu-baseline", "--no-tree-scenes"], env, tmp_path, timeout=1800)
     assert codes == [0] * world, (codes, stdout[0][-2000:], stderr)
     lines = [[l for l in out.splitlines() if l.startswith("{")] for out in stdout]
     assert len(lines[0]) == 1 and not any(lines[1:]), stdout[0][-2000:]

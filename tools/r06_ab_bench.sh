@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; tag=$1; shift; O=$R/gpurun_out/$tag; mkdir 
 for rep in 1 2; do
 for lib in "$@"; do
   if [ "$lib" = product ]; then arg=""; else arg="--hip-lib $R/variants/lib_$lib.so"; fi
-  python bench.py --no-tree-scenes --no-c4-strong --no-cpu-baseline --steps 20 --warmup 5 $arg > $O/$lib.$rep.json 2> $O/$lib.$rep.err
+  python bench.py --full --no-tree-scenes --no-c4-strong --no-cpu-baseline --steps 20 --warmup 5 $arg > $O/$lib.$rep.json 2> $O/$lib.$rep.err
   python - <<PY | tee -a $O/summary.txt
 import json
 d=json.loads(open("$O/$lib.$rep.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; tag=$1; shift; O=$R/gpurun_out/$tag; mkdir -p $O
 for lib in "$@"; do
   if [ "$lib" = product ]; then arg=""; else arg="--hip-lib $R/variants/lib_$lib.so"; fi
-  python bench.py --no-tree-scenes --no-cpu-baseline --no-pmc --steps 5 --warmup 2 $arg > $O/$lib.json 2> $O/$lib.err
+  python bench.py --full --no-tree-scenes --no-cpu-baseline --no-pmc --steps 5 --warmup 2 $arg > $O/$lib.json 2> $O/$lib.err
   python - <<PY | tee -a $O/summary.txt
 import json
 d=json.loads(open("$O/$lib.json").read().strip().splitlines()[-1])

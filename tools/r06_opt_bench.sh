@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; tag=$1; shift; O=$R/gpurun_out/$tag; mkdir 
 for rep in 1 2; do i=0
 for opt in "$@"; do i=$((i+1))
   if [ "$opt" = "-" ]; then arg=""; else arg="--native-option $opt"; fi
-  python bench.py --no-tree-scenes --no-c4-strong --no-cpu-baseline --no-pmc --steps 20 --warmup 5 $arg > $O/$i.$rep.json 2> $O/$i.$rep.err
+  python bench.py --full --no-tree-scenes --no-c4-strong --no-cpu-baseline --no-pmc --steps 20 --warmup 5 $arg > $O/$i.$rep.json 2> $O/$i.$rep.err
   python - <<PY | tee -a $O/summary.txt
 import json
 d=json.loads(open("$O/$i.$rep.json").read().strip().splitlines()[-1]); k=d["kernel_only"]

@@ -5,7 +5,7 @@ T=${2:-tests -m gpu}
 timeout 2400 python -m pytest $T -x -q -s > $O/gputests.log 2>&1; echo "pytest rc=$?" >> $O/gputests.log
 grep -v "^$" $O/gputests.log | tail -${TAILN:-12} | cut -c1-400
 if [ "${NOBENCH:-0}" != 1 ]; then
-timeout 1200 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
+timeout 1200 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
