@@ -179,6 +179,14 @@ typedef struct psdr_scene_desc {
    psdr_render_d_rev that asks for a geometry table (tri_info / cam_to_world) runs the adjoint kernel on it (cbox 512^2 x 64: 0.85 + 4.86 -> 1.25 + 4.0 ms).
    Ignored wherever neither applies (other integrators, paths deeper than 8, more slots than one chunk, option rev_split = 0). */
 #define PSDR_FLAG_KEEP_RECORDS 8
+/* psdr_render_d_fwd / psdr_render_d_rev with PSDR_INTEGRATOR_PATH: evaluate the secondary-edge boundary term of the PathTracer on the slots
+   sppse / sppse_begin / sppse_end name (per slot a direct-source and an indirect-source boundary segment, each with a random
+   walk of camera connections on the sensor side; max_depth = 1 is DirectIntegrator(1, 1)'s term draw for draw).  A slot of sampler 2 then
+   consumes 11 max_depth - 9 draws (3 at max_depth = 1).  max_depth <= 8; a guiding grid is not supported.  Without the flag a PathTracer call
+   ignores sppse, as it always did; other integrators ignore the flag.  Scene options pt_sedge (3: both segments, 1: direct source only,
+   2: indirect source only, 0: neither) and pt_sedge_walk (0: the walk stops at its first vertex) are A/B switches for tests. */
+#define PSDR_FLAG_PATH_SEDGES 16
+#define PSDR_PATH_SEDGES_MAX_DEPTH 8
 
 /* One render call = Integrator::renderC / renderD on one shard of the sample
    slots (src/integrator/integrator.cpp:13-119, src/integrator/direct.cpp). */
@@ -236,7 +244,7 @@ int psdr_scene_destroy(psdr_scene_t h);
 /* Developer options of a handle -- the A/B switches of tools and tests (the reference has none: its strategies are fixed by OptiX and
    Enoki); the library reads NO environment variable.  Names (value): bvh_refit, tiny_scene, two_level, wf_binned, wf_traced, sort_edges,
    tiny_variants, sink_private, aa_prims (0 / 1); bvh_build (1 device, 0 host, -1 by size); wide (0: never the 4-wide tree in the render kernels);
-   rev_split, sedge_split (1 / 0 force, -1 default rule); keep_records (0: PSDR_FLAG_KEEP_RECORDS is ignored); logd (0: PathTracer forward mode with tangents on
+   rev_split, sedge_split (1 / 0 force, -1 default rule); pt_sedge (3 / 1 / 2 / 0) and pt_sedge_walk (0 / 1): see PSDR_FLAG_PATH_SEDGES; keep_records (0: PSDR_FLAG_KEEP_RECORDS is ignored); logd (0: PathTracer forward mode with tangents on
    diffuse albedo texels only runs the dual-number kernel, never the log-derivative one); rev_sorted (0: reverse PathTracer kernels
    scatter row adjoints on the spot); wf_geo (0: PathTracer geometry tangents through the fused kernel); tangent_live (0: no liveness mask); forest_min_inline (inline triangles a two-level tree needs at least, default 6); scratch_plain (1: scratch blocks of 64 MB and more come from hipMalloc instead of the stream-ordered pool -- process-wide, an experiment on TLB reach);
    own_pixels (0: the camera kernels always add to the image with atomics, also where one wave holds all samples of a pixel); emitter_pretest (0: BSDF-sampled rays whose hit matters only on an emitter -- DirectIntegrator, a PathTracer path's last vertex -- are traced without

@@ -622,6 +622,12 @@ int make_ctx(psdr_scene_s *h, const psdr_render_opts *o, int sampler, LaunchCtx 
     return 0;
 }
 
+// PSDR_FLAG_PATH_SEDGES keeps a slot's source sums in registers: max_depth - 1 <= 7 of them
+int check_path_sedges(const psdr_render_opts *o) {
+    if (o->integrator == PSDR_INTEGRATOR_PATH && (o->flags & PSDR_FLAG_PATH_SEDGES) != 0 && o->sppse > 0 && o->max_depth > PSDR_PATH_SEDGES_MAX_DEPTH)
+        return fail("PSDR_FLAG_PATH_SEDGES: PathTracer max_depth > 8 is not supported for the secondary-edge term");
+    return 0;
+}
 int check_counts(const psdr_scene_s *h, const psdr_render_opts *o) {
     const long long WH = (long long) h->desc.width * h->desc.height;
     if (WH <= 0) return fail("Invalid film resolution");
@@ -998,6 +1004,21 @@ const VariantOps *variant_of(const psdr_scene_s *h) {
         default: return variant_ops_6();      // 6; psdr_bvh_build never builds a two-level tree under an environment map
     }
 }
+// the same choice for the kernels of psdr_path_sedge.hip
+const PathSedgeOps *path_sedge_of(const psdr_scene_s *h) {
+    int fl = (h->desc.env_emitter >= 0 ? kSceneEnv : 0) | (h->has_rough ? kSceneRough : 0) | (h->n_blas > 0 ? kSceneForest : 0);
+    if (tiny_tables_ok(h)) fl |= kSceneTiny;
+    switch (fl) {
+        case 0: return path_sedge_ops_0();
+        case 1: return path_sedge_ops_1();
+        case 2: return path_sedge_ops_2();
+        case 3: return path_sedge_ops_3();
+        case 4: return path_sedge_ops_4();
+        case 8: return path_sedge_ops_8();
+        case 10: return path_sedge_ops_10();
+        default: return path_sedge_ops_6();
+    }
+}
 }  // namespace psdr_host
 using namespace psdr_host;
 
@@ -1057,6 +1078,8 @@ int psdr_scene_set_option(psdr_scene_t h, const char *name, double value) {
     else if (n == "keep_records") h->opt.keep_records = iv;              // 0: psdr_render_c ignores PSDR_FLAG_KEEP_RECORDS
     else if (n == "rev_sorted") h->opt.rev_sorted = iv;                  // 0: the reverse camera kernels scatter every row adjoint on the spot (no deferred, sorted adds)
     else if (n == "sedge_split") h->opt.sedge_split = iv;
+    else if (n == "pt_sedge") h->opt.pt_sedge = iv & 3;                  // bit 0: direct-source segment, bit 1: indirect-source segment (0: neither)
+    else if (n == "pt_sedge_walk") h->opt.pt_sedge_walk = iv;
     else if (n == "probe") h->opt.probe = iv;
     else if (n == "trace_wg2") h->opt.trace_wg2 = iv;                    // dense trace kernel as two workgroups per CU: -1 by forest and launch size, 0 never, n > 0 always (stack columns of n entries)
     else if (n == "chunk_log2") h->opt.chunk_log2 = std::max(0, std::min(30, iv));
@@ -1408,10 +1431,12 @@ int psdr_render_d_fwd(psdr_scene_t h, const psdr_render_opts *o, int32_t K, cons
     if (!h || !o || !out_img || !out_dimg || !tangents) return fail("psdr_render_d_fwd: null argument");
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (int rc = check_counts(h, o)) return rc;
+    if (int rc = check_path_sedges(o)) return rc;
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
     if (K != 1 && K != 3) return fail("psdr_render_d_fwd: K must be 1 or 3");
-    return variant_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s);
+    if (int rc = variant_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s)) return rc;
+    return path_sedge_of(h)->fwd(h, o, K, tangents, out_dimg, s);          // PSDR_FLAG_PATH_SEDGES (nothing without it)
 }
 
 int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads,
@@ -1419,6 +1444,7 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
     if (!h || !o || !adj_img || !grads) return fail("psdr_render_d_rev: null argument");
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (int rc = check_counts(h, o)) return rc;
+    if (int rc = check_path_sedges(o)) return rc;
     if (o->flags & PSDR_FLAG_LITERAL_FORMS) return fail("psdr_render_d_rev: PSDR_FLAG_LITERAL_FORMS is a forward-mode diagnostic (no literal-form adjoint)");
     if (o->integrator == PSDR_INTEGRATOR_PATH && o->max_depth > kMaxRevDepthDeep)
         return fail("psdr_render_d_rev: PathTracer max_depth > 250 is not supported in reverse mode");
@@ -1426,7 +1452,8 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
     if (int rc = begin_call(h, s)) return rc;
     std::fill(std::begin(h->rev_layout), std::end(h->rev_layout), 0);
     h->rev_layout[8] = -1;                                                // (no camera launch)
-    return variant_of(h)->render_rev(h, o, adj_img, out_img, grads, s);
+    if (int rc = variant_of(h)->render_rev(h, o, adj_img, out_img, grads, s)) return rc;
+    return path_sedge_of(h)->rev(h, o, adj_img, grads, s);                 // PSDR_FLAG_PATH_SEDGES (nothing without it)
 }
 
 int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *o, const int32_t reso[4], int32_t nrounds, float *out_mass, void *stream) {

@@ -166,6 +166,8 @@ struct psdr_scene_options {
     int logd = 1;                          // PathTracer forward mode with tangents on diffuse albedo texels only: the log-derivative kernel (0: always dual numbers)
     int keep_records = 1;                  // psdr_render_c honours PSDR_FLAG_KEEP_RECORDS (0: ignored -- A/B, tests)
     int rev_sorted = 1;                    // reverse camera kernels with geometry gradients: complete row adjoints wait in LDS and leave sorted by row at the slot's end (0: scattered on the spot)
+    int pt_sedge = 3;                      // PSDR_FLAG_PATH_SEDGES: segments evaluated per slot (bit 0: direct source, bit 1: indirect source) -- A/B, tests
+    int pt_sedge_walk = 1;                 //                        0: the sensor-side walk stops at its first vertex
     int sedge_split = -1;                  // secondary-edge term as filter + survivor kernel: 1 / 0 force, -1 from 2^18 slots
     int chunk_log2 = 0;                    // log2 of the slots per chunk of the chunked launches (0: 2^24 / 2^25, the traced wavefront 2^26)
     int probe = 1;                         // two-level scenes: fused kernels as probe pass + dense trace kernel + final pass where that is built (0: one kernel)
@@ -329,6 +331,19 @@ struct VariantOps {
     int (*render_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, hipStream_t s);
     int (*guide)(psdr_scene_s *h, LaunchCtx &cx, const int32_t reso[4], int nrounds, long long n, float *out_mass, hipStream_t s);
 };
+// The PathTracer's secondary-edge term (PSDR_FLAG_PATH_SEDGES) per flag set: psdr_path_sedge.hip, one more translation unit per set
+struct PathSedgeOps {
+    int (*fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *dimg, hipStream_t s);
+    int (*rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, hipStream_t s);
+};
+const PathSedgeOps *path_sedge_ops_0();
+const PathSedgeOps *path_sedge_ops_1();
+const PathSedgeOps *path_sedge_ops_2();
+const PathSedgeOps *path_sedge_ops_3();
+const PathSedgeOps *path_sedge_ops_4();
+const PathSedgeOps *path_sedge_ops_6();
+const PathSedgeOps *path_sedge_ops_8();
+const PathSedgeOps *path_sedge_ops_10();
 const VariantOps *variant_ops_0();
 const VariantOps *variant_ops_1();
 const VariantOps *variant_ops_2();

@@ -1,0 +1,208 @@
+// psdr_path_sedge.hip -- the kernels of the PathTracer's secondary-edge term (PSDR_FLAG_PATH_SEDGES, psdr_path_sedge.h) for the scene flag set
+// PSDR_VARIANT_FLAGS, and their launches.  A translation unit of its own, compiled once per flag set like psdr_variant.hip: with the kernels inside
+// psdr_kernels.h the units of psdr_variant.hip compiled their EXISTING kernels to other code (flag set 3 then tripped the build's spill guard in
+// k_camera<Dual<3>, Dual<3>>, which this term never runs); kept apart, those units compile the device code they always did.  The C ABI calls
+// path_sedge_ops_<flags>() after the variant's own render_fwd / render_rev (psdr_hip.hip).
+#ifndef PSDR_WIDE_TREE
+#if PSDR_VARIANT_FLAGS == 6
+#define PSDR_WIDE_TREE 1
+#else
+#define PSDR_WIDE_TREE 0
+#endif
+#endif
+#ifndef PSDR_LEAF_PAIR
+#if PSDR_VARIANT_FLAGS == 6
+#define PSDR_LEAF_PAIR 1
+#else
+#define PSDR_LEAF_PAIR 0
+#endif
+#endif
+#include "psdr_kernels.h"
+#include "psdr_path_sedge.h"
+
+#ifndef PSDR_VARIANT_FLAGS
+#error "compile with -DPSDR_VARIANT_FLAGS=0|1|2|3|4|6|8|10"
+#endif
+#define PSDR_CAT2(a, b) a##b
+#define PSDR_CAT(a, b) PSDR_CAT2(a, b)
+
+namespace {
+
+// ---------------------------------------------------------------------- k_path_sedge
+// The secondary-edge term of the PathTracer (PSDR_FLAG_PATH_SEDGES, psdr_path_sedge.h).  A slot evaluates two boundary segments; either is over after its
+// first two rays for most slots, and a survivor then runs up to d-1 walk bounces (and, segment B, up to d-1 source bounces).  Split launch: per segment a
+// filter over all slots (k_secondary_edge_filter for segment A: the very predicate of DirectIntegrator's term; k_path_sedge_filter for segment B), then this
+// kernel over the compacted survivor list with po.seg naming the one segment the list belongs to.  Small launches run it once over all slots, both segments.
+template <int FL>
+__global__ __launch_bounds__(kBlock, 4) void k_path_sedge_filter(LaunchCtx cx, long long i0, long long n, uint32_t *__restrict__ list, int *__restrict__ list_n, unsigned long long *counters) {
+    TraversalStack st; setup_lds(cx, st);
+    uint32_t nrays = 0;
+    const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
+    const int lane = threadIdx.x & 63;
+    for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
+        bool keep = false;
+        if (j < n) {
+            Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
+            const float s0 = rng.next();
+            (void) rng.next(); (void) rng.next();
+            keep = path_sedge_survives_b<FL>(cx.sc, st, rng, s0, nrays);
+        }
+        // (one atomic per wave and trip -- not the per-wave LDS buffer of k_secondary_edge_filter: 6-9 % of the slots pass this predicate, nearly every wave appends)
+        const unsigned long long mask = __ballot(keep);
+        if (mask != 0ull) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(list_n, (int) __popcll(mask));
+            base = __shfl(base, 0, 64);
+            if (keep) list[base + (int) __popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t) j;
+        }
+    }
+    count_rays(counters, nrays);
+}
+
+template <int K, int FL>
+__global__ __launch_bounds__(kBlock) void k_path_sedge(LaunchCtx cx, TangentView<K, FL> tv, long long i0, long long n, float inv_sppse, float *__restrict__ dimg, long long plane,
+                                                       unsigned long long *counters, const uint32_t *__restrict__ list, const int *__restrict__ list_n, PathSedgeOpts po) {
+    using R = Dual<K>;
+    TraversalStack st; setup_lds(cx, st);
+    uint32_t nrays = 0;
+    if (list != nullptr) n = *list_n;
+    for (long long jj = (long long) blockIdx.x * kBlock + threadIdx.x; jj < n; jj += (long long) gridDim.x * kBlock) {
+        const long long j = list != nullptr ? (long long) list[jj] : jj;
+        Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
+        const float s3[3] = {rng.next(), rng.next(), rng.next()};
+        path_secondary_edge_sample<R>(cx.sc, tv, st, rng, s3, po, nrays, list == nullptr, [&](int pixel, const Vec3<R> &value) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float g[3] = {value.x.d[k] * inv_sppse, value.y.d[k] * inv_sppse, value.z.d[k] * inv_sppse};
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    if (g[c] != 0.f) atomicAdd(dimg + (size_t) k * plane + (size_t) pixel * 3 + c, g[c]);
+            }
+        });
+    }
+    count_rays(counters, nrays);
+}
+
+template <int FL>
+__global__ __launch_bounds__(kBlock) void k_path_sedge_rev(LaunchCtx cx, DeviceSink<FL> sink, long long i0, long long n, float inv_sppse, const float *__restrict__ adj_img,
+                                                           unsigned long long *counters, const uint32_t *__restrict__ list, const int *__restrict__ list_n, PathSedgeOpts po) {
+    TraversalStack st; setup_lds(cx, st);
+    sink.begin(dyn_lds_floats(cx.off_sink));
+    uint32_t nrays = 0;
+    if (list != nullptr) n = *list_n;
+    for (long long jj = (long long) blockIdx.x * kBlock + threadIdx.x; jj < n; jj += (long long) gridDim.x * kBlock) {
+        const long long j = list != nullptr ? (long long) list[jj] : jj;
+        Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
+        const float s3[3] = {rng.next(), rng.next(), rng.next()};
+        path_secondary_edge_reverse(sink, cx.sc, st, rng, s3, po, inv_sppse, adj_img, nrays, list == nullptr);
+    }
+    sink.end();
+    count_rays(counters, nrays);
+}
+
+
+// ---- launches of the PathTracer's secondary-edge term (PSDR_FLAG_PATH_SEDGES)
+inline bool path_sedges_wanted(const psdr_scene_s *h, const psdr_render_opts *o) {
+    return o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0 && o->integrator == PSDR_INTEGRATOR_PATH && (o->flags & PSDR_FLAG_PATH_SEDGES) != 0;
+}
+inline bool path_sedge_split(const psdr_scene_s *h, long long n) {          // the rule of secondary_edge_filter
+    const int split_env = h->opt.sedge_split;
+    return !(split_env == 0 || (split_env < 0 && n < (1ll << 18))) && n <= 0x7fffffffLL;
+}
+// filter pass of segment B: the survivor list shares the handle's block with segment A's (the passes of one call follow each other on the stream)
+template <int FL>
+int path_sedge_filter_b(psdr_scene_s *h, const LaunchCtx &cx, long long i0, long long n, const uint32_t **list, const int **list_n, hipStream_t s) {
+    const size_t need = 256 + (size_t) n * sizeof(uint32_t);
+    if (int rc = scratch_reserve(&h->d_se_list, &h->se_list_bytes, need, s, "secondary-edge survivor list")) return rc;
+    int *cnt = reinterpret_cast<int *>(h->d_se_list);
+    uint32_t *lst = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(h->d_se_list) + 256);
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_path_sedge_filter<FL>, dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, i0, n, lst, cnt, h->d_counters);
+    HIP_TRY(hipGetLastError());
+    *list = lst; *list_n = cnt;
+    return 0;
+}
+// launch(list, list_n, grid slots, po) starts the evaluating kernel (forward or reverse); cxf: the context the filters stage the scene with
+template <int FL, class Launch>
+int path_sedge_passes(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCtx &cxf, long long i0, long long n, hipStream_t s, Launch &&launch) {
+    if (h->desc.guide_cmf != nullptr && h->desc.num_guide_cells > 0) return fail("PSDR_FLAG_PATH_SEDGES: a guiding grid is not supported for PathTracer slots");
+    PathSedgeOpts po{o->max_depth, h->opt.pt_sedge & 3, h->opt.pt_sedge_walk};
+    if (po.max_depth < 2) po.seg &= 1;
+    if (!path_sedge_split(h, n)) {
+        if (po.seg != 0) { launch(nullptr, nullptr, n, po); HIP_TRY(hipGetLastError()); }
+        return 0;
+    }
+    if (po.seg & 1) {
+        const uint32_t *list = nullptr; const int *list_n = nullptr;
+        if (int rc = secondary_edge_filter<FL>(h, cxf, i0, n, &list, &list_n, s)) return rc;
+        PathSedgeOpts pa = po; pa.seg = 1;
+        launch(list, list_n, list ? std::max(n / 16, 1ll << 16) : n, pa);
+        HIP_TRY(hipGetLastError());
+    }
+    if (po.seg & 2) {
+        const uint32_t *list = nullptr; const int *list_n = nullptr;
+        if (int rc = path_sedge_filter_b<FL>(h, cxf, i0, n, &list, &list_n, s)) return rc;
+        PathSedgeOpts pb = po; pb.seg = 2;
+        launch(list, list_n, std::max(n / 4, 1ll << 16), pb);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+template <int K, int FL>
+int path_sedge_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tangents *tangents, float *dimg, hipStream_t s) {
+    const long long WH = (long long) h->desc.width * h->desc.height;
+    TangentView<K, FL> tv;
+    for (int k = 0; k < K; ++k) tv.t[k] = tangents[k];
+    LaunchCtx cx;
+    if (int rc = make_ctx(h, o, 2, cx)) return rc;
+    const long long i0 = WH * o->sppse_begin, n = WH * (o->sppse_end - o->sppse_begin);
+    h->slots[2] += (uint64_t) n;
+    return path_sedge_passes<FL>(h, o, cx, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppse,
+                           dimg, WH * 3, h->d_counters, list, list_n, po);
+    });
+}
+// forward mode: adds the term to the K derivative images psdr_render_d_fwd has rendered (same stream)
+template <int FL>
+int path_sedge_fwd(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *dimg, hipStream_t s) {
+    if (!path_sedges_wanted(h, o)) return 0;
+    return K == 1 ? path_sedge_fwd_k<1, FL>(h, o, tangents, dimg, s) : path_sedge_fwd_k<3, FL>(h, o, tangents, dimg, s);
+}
+// reverse mode: scatters the term's adjoints into the tables psdr_render_d_rev has filled (same stream, same gradient cache layout)
+template <int FL>
+int path_sedge_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, hipStream_t s) {
+    if (!path_sedges_wanted(h, o)) return 0;
+    const long long WH = (long long) h->desc.width * h->desc.height;
+    DeviceSink<FL> sink{}; sink.g = *grads; sink.L = make_sink_layout(h, grads);
+    if ((FL & kSceneTiny) != 0 && PSDR_TINY_DIRECT_ROWS && grads->g_tri_info != nullptr && !(h->hot_identity && sink.L.hot_rows == h->desc.num_tris))
+        return fail("psdr_render_d_rev: the gradient cache of a scene without a tree does not hold every triangle row");
+    LaunchCtx cx;
+    if (int rc = make_ctx(h, o, 2, cx)) return rc;
+    const long long i0 = WH * o->sppse_begin, n = WH * (o->sppse_end - o->sppse_begin);
+    h->slots[2] += (uint64_t) n;
+    sink.L.priv_rows = 0; sink.L.priv_emitter = -1; sink.L.priv_regs = 0;          // as the DirectIntegrator's secondary-edge kernel: no private rows, nothing deferred
+    sink.L.pend_rows = 0; sink.L.pend_off = 0;
+    const int cache_bytes = sink_bytes(sink.L);
+    plan_lds(h, cx, cache_bytes);
+    cx.off_sink = lds_bytes(cx, h);
+    const int dyn_bytes = cx.off_sink + cache_bytes;
+    if (dyn_bytes > h->lds_limit) return fail("psdr_render_d_rev: the secondary-edge launch needs " + std::to_string(dyn_bytes) + " bytes of LDS per workgroup");
+    if (dyn_bytes > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_path_sedge_rev<FL>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes));
+    LaunchCtx cxf;                                              // the filters stage the scene like a forward kernel (no gradient cache in LDS)
+    if (int rc = make_ctx(h, o, 2, cxf)) return rc;
+    return path_sedge_passes<FL>(h, o, cxf, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po) {
+        hipLaunchKernelGGL(k_path_sedge_rev<FL>, dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, cx, sink, i0, n, 1.f / (float) o->sppse, adj_img,
+                           h->d_counters, list, list_n, po);
+    });
+}
+}  // namespace
+
+namespace psdr_host {
+const PathSedgeOps *PSDR_CAT(path_sedge_ops_, PSDR_VARIANT_FLAGS)() {
+    constexpr int FL = PSDR_VARIANT_FLAGS;
+    static const PathSedgeOps ops{&path_sedge_fwd<FL>, &path_sedge_rev<FL>};
+    return &ops;
+}
+}  // namespace psdr_host

@@ -26,7 +26,8 @@ BSDF_DIFFUSE, BSDF_ROUGHCONDUCTOR = 0, 1
 SLOT_REFLECTANCE, SLOT_ALPHA_U, SLOT_ALPHA_V, SLOT_ETA, SLOT_K = range(5)
 CAM_SAMPLE_TO_CAMERA, CAM_TO_WORLD, CAM_WORLD_TO_SAMPLE, CAM_POS, CAM_DIR, CAM_INV_AREA = 0, 16, 32, 48, 51, 54
 INTEGRATOR_DIRECT, INTEGRATOR_PATH, INTEGRATOR_FIELD = 0, 1, 2
-FLAG_FUSED, FLAG_WAVEFRONT, FLAG_LITERAL_FORMS, FLAG_KEEP_RECORDS = 1, 2, 4, 8
+FLAG_FUSED, FLAG_WAVEFRONT, FLAG_LITERAL_FORMS, FLAG_KEEP_RECORDS, FLAG_PATH_SEDGES = 1, 2, 4, 8, 16
+MAX_PATH_SEDGE_DEPTH = 8          # csrc/psdr_path_sedge.h kMaxPathSedgeDepth
 FIELDS = {"silhouette": 0, "position": 1, "depth": 2, "geoNormal": 3, "shNormal": 4, "uv": 5}
 
 _fp = C.c_void_p  # all table pointers travel as raw addresses
@@ -214,4 +215,7 @@ def draws_per_slot(opts):
         li = 5 * opts.max_depth
     else:
         li = 0
-    return (2 + li, 1 + 2 * li, 3)
+    se = 3
+    if opts.integrator == INTEGRATOR_PATH and (opts.flags & FLAG_PATH_SEDGES) and opts.max_depth >= 2:
+        se = 11 * opts.max_depth - 9          # s3, 2 direction numbers, 3 (d-1) + 3 (d-2) walk numbers, 5 (d-1) source-bounce numbers (csrc/psdr_path_sedge.h)
+    return (2 + li, 1 + 2 * li, se)

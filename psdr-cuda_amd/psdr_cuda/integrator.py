@@ -217,13 +217,17 @@ class Integrator(Object):
         dist = _dist()
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
         sppe = o.sppe if with_edges else 0
-        sppse = o.sppse if (with_edges and self._kind == _abi.INTEGRATOR_DIRECT) else 0
+        path_sedges = self._kind == _abi.INTEGRATOR_PATH and getattr(self, "secondary_edges", False)
+        sppse = o.sppse if (with_edges and (self._kind == _abi.INTEGRATOR_DIRECT or path_sedges)) else 0
+        if sppse > 0 and path_sedges and self.max_depth > _abi.MAX_PATH_SEDGE_DEPTH:
+            raise RuntimeError("PathTracer(secondary_edges=True): max_depth > %d is not supported for the secondary-edge term" % _abi.MAX_PATH_SEDGE_DEPTH)
         opts = _abi.make_opts(
             integrator=self._kind, bsdf_samples=getattr(self, "bsdf_samples", 1), light_samples=getattr(self, "light_samples", 1),
             max_depth=getattr(self, "max_depth", 1), hide_emitters=getattr(self, "hide_emitters", False),
             field=getattr(self, "_field_id", 0), spp=o.spp, sppe=sppe, sppse=sppse,
             spp_range=shard_range(o.spp, rank, world), sppe_range=shard_range(sppe, rank, world),
-            sppse_range=shard_range(sppse, rank, world), rng_offset=scene._rng_offset)
+            sppse_range=shard_range(sppse, rank, world), rng_offset=scene._rng_offset,
+            flags=_abi.FLAG_PATH_SEDGES if (path_sedges and sppse > 0) else 0)
         return opts
 
     def _advance_rng(self, scene, opts):
@@ -415,13 +419,20 @@ class DirectIntegrator(Integrator):
 
 class PathTracer(Integrator):
     """Multi-bounce extension of DirectIntegrator::__Li.  NOT in the reference snapshot (SURVEY F2,
-    App. F): defined so that PathTracer(max_depth=1) == DirectIntegrator(1, 1) sample for sample."""
+    App. F): defined so that PathTracer(max_depth=1) == DirectIntegrator(1, 1) sample for sample.
+
+    secondary_edges=True: renderD also evaluates the secondary-edge boundary term (moving shadow and occlusion boundaries under global illumination,
+    SURVEY App. F, F3) on scene.opts.sppse slots per pixel, in forward and reverse mode; max_depth <= 8.  Without it the geometry gradient of renderD
+    holds the interior and the primary-edge term only and is wrong wherever a shadow edge moves.  The default is False because turning the term on
+    changes the results of existing callers; a later change may flip it.  preprocess_secondary_edges stays a DirectIntegrator feature (these slots are
+    not guided)."""
     _type_name = "PathTracer"
     _kind = _abi.INTEGRATOR_PATH
 
-    def __init__(self, max_depth=3):
+    def __init__(self, max_depth=3, secondary_edges=False):
         super().__init__()
         psdr_assert(max_depth >= 1)
         self.max_depth = int(max_depth)
+        self.secondary_edges = bool(secondary_edges)
         self.bsdf_samples = self.light_samples = 1
         self.hide_emitters = False
