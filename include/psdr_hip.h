@@ -246,10 +246,13 @@ int psdr_scene_destroy(psdr_scene_t h);
    tiny_variants, sink_private, aa_prims (0 / 1); bvh_build (1 device, 0 host, -1 by size); wide (0: never the 4-wide tree in the render kernels);
    rev_split, sedge_split (1 / 0 force, -1 default rule); pt_sedge (3 / 1 / 2 / 0) and pt_sedge_walk (0 / 1): see PSDR_FLAG_PATH_SEDGES; keep_records (0: PSDR_FLAG_KEEP_RECORDS is ignored); logd (0: PathTracer forward mode with tangents on
    diffuse albedo texels only runs the dual-number kernel, never the log-derivative one); rev_sorted (0: reverse PathTracer kernels
-   scatter row adjoints on the spot); wf_geo (0: PathTracer geometry tangents through the fused kernel); tangent_live (0: no liveness mask); forest_min_inline (inline triangles a two-level tree needs at least, default 6); scratch_plain (1: scratch blocks of 64 MB and more come from hipMalloc instead of the stream-ordered pool -- process-wide, an experiment on TLB reach);
+   scatter row adjoints on the spot); wf_geo (0: PathTracer geometry tangents through the fused kernel); tangent_live (0: no liveness mask); forest_min_inline (inline triangles a two-level tree needs at least, default 0); scratch_plain (1: scratch blocks of 64 MB and more come from hipMalloc instead of the stream-ordered pool -- process-wide, an experiment on TLB reach);
    own_pixels (0: the camera kernels always add to the image with atomics, also where one wave holds all samples of a pixel); emitter_pretest (0: BSDF-sampled rays whose hit matters only on an emitter -- DirectIntegrator, a PathTracer path's last vertex -- are traced without
    first meeting the emitters' primitives); occ_rows (0: the light rays of a scene without a tree test every kernel-argument primitive instead of
    the ones that can lie between the path vertex and the emitter sample); probe (0: no probe / trace / final launches);
+   seed_cache (1 default: the fused PathTracer renderC launches on a scene without a tree load the seeded PCG32 state of
+   their sample slots from a read-only table on the handle, filled once per (width * height, spp, spp range); 0: every kernel seeds its streams itself; same results
+   either way); seed_cache_log2 (the largest launch that table serves, log2 of its slots at 16 bytes each: default 25 = 512 MB; larger launches seed themselves);
    trace_wg2 (dense trace kernel as two workgroups per CU: -1 by forest and launch size, 0 never, n > 0 always with stack columns of n entries);
    chunk_log2 (slots per chunk of the chunked launches, 0 = default); blocks_per_cu, camera_blocks, lds_budget, sink_rep, bvh_maxleaf (integers,
    0 = default where that makes sense); bvh_tcost (float).  Unknown names fail.  Options that change the tree take effect at the next psdr_bvh_build. */
@@ -405,6 +408,10 @@ int psdr_geo_emitter_tables(int32_t M, const float *rows, int32_t row_stride, co
      [11] 1 if the path records live in HBM, [12] [13] cache slots of the private rows, [14] hot rows the tree build chose,
      [15] 1 if the primary-edge slots ran sorted by pixel } */
 int psdr_scene_rev_layout(psdr_scene_t h, int32_t out[16]);
+
+/* Seed table of the handle (option seed_cache; diagnostics): out = { [0] slots the table holds seeds for (0: none), [1] bytes allocated,
+   [2] fills since the handle was created (one per change of width * height, spp or spp range), [3] camera launches served from the table }. */
+int psdr_scene_seed_info(psdr_scene_t h, int64_t out[4]);
 
 /* Counters of the last render call on this handle (host values):
    [0] rays traced, [1] camera slots, [2] primary-edge slots, [3] secondary-edge slots. */

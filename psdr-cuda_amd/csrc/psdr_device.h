@@ -1642,15 +1642,19 @@ PSDR_HD Vec3<M> wavefront_bounce_vertex(const SceneView &sc, const TVT &tv, Trav
 
 // One camera sample slot: Integrator::__render (src/integrator/integrator.cpp:64-95), before the splat
 template <class G, class M, int INTEG = -1, class TVT>
-PSDR_HD Vec3<M> camera_sample(const SceneView &sc, const TVT &tv, TraversalStack &st, const LiParams &lp, const RngJump &jump,
-                              int pixel, uint64_t slot, uint32_t &nrays) {
-    Rng rng; rng.init(slot, jump);
+PSDR_HD Vec3<M> camera_sample(const SceneView &sc, const TVT &tv, TraversalStack &st, const LiParams &lp, Rng rng, int pixel, uint32_t &nrays) {          // (rng: the slot's stream at its first draw of this call)
     const float j0 = rng.next(), j1 = rng.next();
     const int W = sc.d.width;
     const int px = pixel % W, py = pixel / W;
     const float sx = ((float) px + j0) / (float) W, sy = ((float) py + j1) / (float) sc.d.height;
     const RayT<G> ray = primary_ray<G>(sc, tv, sx, sy);
     return zero_nonfinite(Li<G, M, INTEG>(sc, tv, st, lp, rng, ray, true, nrays));
+}
+template <class G, class M, int INTEG = -1, class TVT>
+PSDR_HD Vec3<M> camera_sample(const SceneView &sc, const TVT &tv, TraversalStack &st, const LiParams &lp, const RngJump &jump,
+                              int pixel, uint64_t slot, uint32_t &nrays) {
+    Rng rng; rng.init(slot, jump);
+    return camera_sample<G, M, INTEG>(sc, tv, st, lp, rng, pixel, nrays);
 }
 
 // PSDR_PRIMARY_EDGE_VIS_CHECK (macros.h:13; integrator.cpp:105-108, perspective.cpp:171-196), active when the caller supplies

@@ -1075,6 +1075,8 @@ int psdr_scene_set_option(psdr_scene_t h, const char *name, double value) {
     else if (n == "tangent_live") h->opt.tangent_live = iv;              // 0: forward-mode kernels load the tangents of every triangle row (no liveness mask)
     else if (n == "wf_geo") h->opt.wf_geo = iv;                          // 0: geometry tangents of the PathTracer always through the fused kernel
     else if (n == "logd") h->opt.logd = iv;                              // 0: PathTracer forward mode never runs the log-derivative kernel
+    else if (n == "seed_cache") h->opt.seed_cache = iv;                  // 0: no seed table -- every camera kernel seeds its PCG32 streams itself
+    else if (n == "seed_cache_log2") h->opt.seed_cache_log2 = std::max(0, std::min(40, iv));   // log2 of the largest launch (in slots) the seed table serves (default 25: 512 MB)
     else if (n == "keep_records") h->opt.keep_records = iv;              // 0: psdr_render_c ignores PSDR_FLAG_KEEP_RECORDS
     else if (n == "rev_sorted") h->opt.rev_sorted = iv;                  // 0: the reverse camera kernels scatter every row adjoint on the spot (no deferred, sorted adds)
     else if (n == "sedge_split") h->opt.sedge_split = iv;
@@ -1101,6 +1103,8 @@ int psdr_scene_destroy(psdr_scene_t h) {
     if (h->d_ws) (void) hipFree(h->d_ws);
     if (h->d_live) (void) hipFree(h->d_live);
     if (h->d_logd_bad) (void) hipFree(h->d_logd_bad);
+    if (h->d_seed) (void) hipFree(h->d_seed);
+    if (h->seed_event) (void) hipEventDestroy(h->seed_event);
     if (h->d_hot_map) (void) hipFree(h->d_hot_map);
     if (h->d_hot_tris) (void) hipFree(h->d_hot_tris);
     if (h->d_occ) (void) hipFree(h->d_occ);
@@ -1542,6 +1546,12 @@ int psdr_scene_info(psdr_scene_t h, int32_t out[8]) {
 int psdr_scene_rev_layout(psdr_scene_t h, int32_t out[16]) {
     if (!h || !out) return fail("psdr_scene_rev_layout: null argument");
     std::copy(std::begin(h->rev_layout), std::end(h->rev_layout), out);
+    return 0;
+}
+
+int psdr_scene_seed_info(psdr_scene_t h, int64_t out[4]) {
+    if (!h || !out) return fail("psdr_scene_seed_info: null argument");
+    out[0] = h->seed_valid ? h->seed_key[0] * h->seed_key[3] : 0; out[1] = (int64_t) (h->seed_cap * sizeof(ulonglong2)); out[2] = h->seed_fills; out[3] = h->seed_launches;
     return 0;
 }
 

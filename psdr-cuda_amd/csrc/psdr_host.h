@@ -172,6 +172,8 @@ struct psdr_scene_options {
     int chunk_log2 = 0;                    // log2 of the slots per chunk of the chunked launches (0: 2^24 / 2^25, the traced wavefront 2^26)
     int probe = 1;                         // two-level scenes: fused kernels as probe pass + dense trace kernel + final pass where that is built (0: one kernel)
     int trace_wg2 = -1;                    // the dense trace kernel as two workgroups per CU: -1 by forest and launch size, 0 never, n > 0 always (stack columns of n entries in LDS)
+    int seed_cache = 1;                    // PathTracer renderC launches on a scene without a tree load their PCG32 seeds from the handle's seed table (psdr_kernels.h seed_table); 0: every kernel seeds its streams itself
+    int seed_cache_log2 = 25;              // log2 of the largest launch the seed table serves, in slots (16 bytes each: 512 MB)
     int bvh_maxleaf = 4;                   // host SAH builder: leaf size limit (1..8)
     float bvh_tcost = 2.0f;                //                   cost of a node visit in triangle tests
 };
@@ -271,6 +273,14 @@ struct psdr_scene_s {
     struct KeptRecords { bool valid = false; psdr_render_opts o{}; uint64_t gen = 0; long long n = 0; int kind = 0; } kept;      // kind 1: the traced wavefront's records (c, f per vertex), 0: the value kernel's (suffix radiances)
     uint64_t tables_gen = 0;               // bumped whenever psdr_scene_set_tables installs a descriptor that differs from the current one
 
+    // seed table of the fused PathTracer launches on a scene without a tree (psdr_kernels.h seed_table): 16 bytes per launch-local slot, read-only between fills
+    void *d_seed = nullptr;
+    size_t seed_cap = 0;                   // entries allocated
+    long long seed_key[4] = {0, 0, 0, 0};  // width * height, spp, spp_begin, samples per pixel of the launch the table was filled for
+    bool seed_valid = false;
+    hipStream_t seed_stream = nullptr;     // stream of the fill; seed_event marks its end for launches on other streams
+    hipEvent_t seed_event = nullptr;
+    long long seed_fills = 0, seed_launches = 0;      // psdr_scene_seed_info
     // wavefront PathTracer: path-state streams + stream counters
     void *d_ws = nullptr;
     size_t ws_bytes = 0;

@@ -173,61 +173,94 @@ constexpr int kLogdGateWord = kRayCounterStride - 1;
 template <class G, class R, int INTEG, int FL> constexpr bool logd_instance() {
     return PSDR_LOGD && !is_ad<G>() && is_ad<R>() && INTEG == PSDR_INTEGRATOR_PATH && (FL & (kSceneRough | kSceneEnv | kScenePre)) == 0;
 }
+// Seed table of a scene handle (psdr_scene_s::d_seed): entry j = the PCG32 stream of launch-local slot j at its first draw, (state, inc) = Rng::seed(slot id).  The
+// seeded stream depends on the slot id alone -- not on the scene, the parameters, the call's rng_offset or the kernel -- and costs 168 VALU instructions (84 of them
+// 64-bit integer forms) per slot to recompute, 6.5-6.8 % of a PathTracer(3) path on a scene without a tree.  The streams stay stateless: the table is read-only, the
+// jump-ahead still supplies the offset (Rng::init_seeded).
+__global__ __launch_bounds__(kBlock) void k_seed_fill(ulonglong2 *__restrict__ seed, long long n, int spp, int s_begin, SlotDiv nsp) {
+    const long long j = (long long) blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    int pixel, s_in;
+    slot_to_pixel(j, nsp, pixel, s_in);
+    Rng rng; rng.seed((uint64_t) pixel * (uint64_t) spp + (uint64_t) (s_begin + s_in));
+    seed[j] = ulonglong2{rng.state, rng.inc};
+}
+__device__ __forceinline__ Rng seeded_rng(const ulonglong2 &sd, const RngJump &jump) { Rng rng; rng.init_seeded(sd.x, sd.y, jump); return rng; }
+// The body k_camera and k_camera_seeded share, as a macro: the twin without a table compiles to what it did before there was one (tests/test_isa_guard.py).  SEED_LOAD: first statement of a trip; SAMPLE: the slot's radiance.
+//   own: every pixel's samples of this launch sit in ONE wave (64 % samples per pixel == 0, run_camera) -- the run's head lane STORES the pixel (the image was
+//        zeroed, the edge terms add to the derivative images afterwards) instead of three to twelve returning L2 atomics of 32 bytes each: C2 1.57 M atomics per launch
+//   gate word: the dual-number PathTracer instances a log-derivative launch stands in for (k_camera_logd below) -- both are launched, the gate word says which one runs
+//   kScenePre: final pass of a probe / trace / final launch (DirectIntegrator(1, 1) on a two-level scene) -- the slot's tree hits
+#define PSDR_CAMERA_KERNEL_BODY(SEED_LOAD, SAMPLE) \
+    constexpr int K = ad_traits<R>::K; \
+    constexpr int NV = 3 * (1 + K); \
+    if constexpr (logd_instance<G, R, INTEG, FL>()) { if (counters[kLogdGateWord] == 1ull) return; } \
+    TraversalStack st; setup_lds(cx, st, tv); \
+    uint32_t nrays = 0; \
+    const long long nceil = (n + kBlock - 1) / kBlock * kBlock; \
+    for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) { \
+        const bool in = j < n; \
+        SEED_LOAD \
+        int pixel = 0x7fffffff, s_in = 0; \
+        if (in) slot_to_pixel(j0 + j, nsp, pixel, s_in); \
+        float v[NV]; \
+_Pragma("unroll") \
+        for (int i = 0; i < NV; ++i) v[i] = 0.f; \
+        if constexpr ((FL & kScenePre) != 0) { if (in) probe_load<3>(st, pv, j, pv.mask[j]); } \
+        if (in) { \
+            const int s = s_begin + s_in; \
+            const uint64_t slot = (uint64_t) pixel * (uint64_t) spp + (uint64_t) s; \
+            const Vec3<R> r = SAMPLE; \
+            v[0] = val(r.x) * inv_spp; v[1] = val(r.y) * inv_spp; v[2] = val(r.z) * inv_spp; \
+_Pragma("unroll") \
+            for (int k = 0; k < K; ++k) { \
+                v[3 + 3 * k] = tangent(r.x, k) * inv_spp; v[4 + 3 * k] = tangent(r.y, k) * inv_spp; v[5 + 3 * k] = tangent(r.z, k) * inv_spp; \
+            } \
+        } \
+        const bool head = wave_segmented_sum<NV>(pixel, v); \
+        if (head && in) { \
+            float *p = img + (size_t) pixel * 3; \
+            if (own) { \
+                p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; \
+_Pragma("unroll") \
+                for (int k = 0; k < K; ++k) { float *q = dimg + (size_t) k * plane + (size_t) pixel * 3; q[0] = v[3 + 3 * k]; q[1] = v[4 + 3 * k]; q[2] = v[5 + 3 * k]; } \
+            } else { \
+                if (v[0] != 0.f) atomicAdd(p, v[0]); \
+                if (v[1] != 0.f) atomicAdd(p + 1, v[1]); \
+                if (v[2] != 0.f) atomicAdd(p + 2, v[2]); \
+_Pragma("unroll") \
+                for (int k = 0; k < K; ++k) { \
+                    float *q = dimg + (size_t) k * plane + (size_t) pixel * 3; \
+                    if (v[3 + 3 * k] != 0.f) atomicAdd(q, v[3 + 3 * k]); \
+                    if (v[4 + 3 * k] != 0.f) atomicAdd(q + 1, v[4 + 3 * k]); \
+                    if (v[5 + 3 * k] != 0.f) atomicAdd(q + 2, v[5 + 3 * k]); \
+                } \
+            } \
+        } \
+    } \
+    count_rays(counters, nrays);
+#define PSDR_SEED_LOAD_NONE
+#define PSDR_SEED_LOAD const ulonglong2 sd = in ? seed[j] : ulonglong2{0ull, 0ull};
 template <class G, class R, int INTEG, int FL, bool NOTREE = false>
 __global__ __launch_bounds__(kBlock, (camera_waves<G, R, INTEG, FL, NOTREE>())) void k_camera(LaunchCtx cx, TV<R, FL> tv, int spp, int s_begin, SlotDiv nsp, long long n, float inv_spp,
                                                    float *__restrict__ img, float *__restrict__ dimg, long long plane,
                                                    unsigned long long *counters, long long j0, ProbeView pv, int own) {
-    // own: every pixel's samples of this launch sit in ONE wave (64 % samples per pixel == 0, run_camera) -- the run's head lane STORES the pixel (the image was
-    // zeroed, the edge terms add to the derivative images afterwards) instead of three to twelve returning L2 atomics of 32 bytes each: C2 1.57 M atomics per launch
-    constexpr int K = ad_traits<R>::K;
-    constexpr int NV = 3 * (1 + K);
-    // the dual-number PathTracer instances a log-derivative launch stands in for (k_camera_logd below): both are launched, the gate word says which one runs
-    if constexpr (logd_instance<G, R, INTEG, FL>()) { if (counters[kLogdGateWord] == 1ull) return; }
-    TraversalStack st; setup_lds(cx, st, tv);
-    uint32_t nrays = 0;
-    const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
-    for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
-        const bool in = j < n;
-        int pixel = 0x7fffffff, s_in = 0;
-        if (in) slot_to_pixel(j0 + j, nsp, pixel, s_in);
-        float v[NV];
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] = 0.f;
-        // final pass of a probe / trace / final launch (DirectIntegrator(1, 1) on a two-level scene): the slot's tree hits
-        if constexpr ((FL & kScenePre) != 0) { if (in) probe_load<3>(st, pv, j, pv.mask[j]); }
-        if (in) {
-            const int s = s_begin + s_in;
-            const uint64_t slot = (uint64_t) pixel * (uint64_t) spp + (uint64_t) s;
-            const Vec3<R> r = camera_sample<G, R, INTEG>(cx.sc, tv, st, cx.lp, cx.jump, pixel, slot, nrays);
-            v[0] = val(r.x) * inv_spp; v[1] = val(r.y) * inv_spp; v[2] = val(r.z) * inv_spp;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                v[3 + 3 * k] = tangent(r.x, k) * inv_spp; v[4 + 3 * k] = tangent(r.y, k) * inv_spp; v[5 + 3 * k] = tangent(r.z, k) * inv_spp;
-            }
-        }
-        const bool head = wave_segmented_sum<NV>(pixel, v);
-        if (head && in) {
-            float *p = img + (size_t) pixel * 3;
-            if (own) {
-                p[0] = v[0]; p[1] = v[1]; p[2] = v[2];
-#pragma unroll
-                for (int k = 0; k < K; ++k) { float *q = dimg + (size_t) k * plane + (size_t) pixel * 3; q[0] = v[3 + 3 * k]; q[1] = v[4 + 3 * k]; q[2] = v[5 + 3 * k]; }
-            } else {
-                if (v[0] != 0.f) atomicAdd(p, v[0]);
-                if (v[1] != 0.f) atomicAdd(p + 1, v[1]);
-                if (v[2] != 0.f) atomicAdd(p + 2, v[2]);
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    float *q = dimg + (size_t) k * plane + (size_t) pixel * 3;
-                    if (v[3 + 3 * k] != 0.f) atomicAdd(q, v[3 + 3 * k]);
-                    if (v[4 + 3 * k] != 0.f) atomicAdd(q + 1, v[4 + 3 * k]);
-                    if (v[5 + 3 * k] != 0.f) atomicAdd(q + 2, v[5 + 3 * k]);
-                }
-            }
-        }
-    }
-    count_rays(counters, nrays);
+    PSDR_CAMERA_KERNEL_BODY(PSDR_SEED_LOAD_NONE, (camera_sample<G, R, INTEG>(cx.sc, tv, st, cx.lp, cx.jump, pixel, slot, nrays)))
 }
+// k_camera with the slots' streams loaded from the handle's seed table (launch-local slot j: no chunks, no probe rows): instantiated where seeding is a visible share
+// of the work (run_camera)
+template <class G, class R, int INTEG, int FL, bool NOTREE = false>
+__global__ __launch_bounds__(kBlock, (camera_waves<G, R, INTEG, FL, NOTREE>())) void k_camera_seeded(LaunchCtx cx, TV<R, FL> tv, int spp, int s_begin, SlotDiv nsp, long long n, float inv_spp,
+                                                   float *__restrict__ img, float *__restrict__ dimg, long long plane,
+                                                   unsigned long long *counters, int own, const ulonglong2 *__restrict__ seed) {
+    static_assert((FL & kScenePre) == 0, "seeded launches have no probe rows");
+    constexpr long long j0 = 0;
+    const ProbeView pv{nullptr, nullptr};
+    PSDR_CAMERA_KERNEL_BODY(PSDR_SEED_LOAD, (((void) slot), camera_sample<G, R, INTEG>(cx.sc, tv, st, cx.lp, seeded_rng(sd, cx.jump), pixel, nrays)))
+}
+#undef PSDR_CAMERA_KERNEL_BODY
+#undef PSDR_SEED_LOAD
+#undef PSDR_SEED_LOAD_NONE
 
 // ---------------------------------------------------------------- log-derivative launches (round 5)
 // k_logd_check: the gate.  One thread per texel: a texel some tangent set moves must have an albedo the quotient d rho / rho can be formed with.
@@ -1724,6 +1757,38 @@ inline long long launch_chunk(const psdr_scene_s *h, int log2_default) { return 
 inline bool probe_direct(const psdr_scene_s *h, const psdr_render_opts *o, long long n) {
     return traced_wavefront(h) && h->opt.probe != 0 && o->bsdf_samples == 1 && o->light_samples == 1 && !(o->flags & PSDR_FLAG_FUSED) && n >= (1ll << 16);
 }
+// The handle's seed table for a fused camera launch of n = WH * nsp slots on stream s (k_seed_fill above), or nullptr: the launch runs the kernels that seed their
+// streams themselves -- option seed_cache 0, a launch above 2^seed_cache_log2 slots (16 bytes per slot: 512 MB at the default 25; the 1024^2 x 512 spp launches of
+// BASELINE configs[4] would need 8.6 GB), or no memory for the table (not an error).  The table is keyed by what fixes slot j's id, (WH, spp, spp_begin, nsp): in an
+// optimisation loop that is fixed for thousands of calls, so the fill runs once; it is stream-ordered, without host synchronisation or read-back.
+// Like the handle's other scratch buffers the table belongs to ONE stream at a time: a refill or a reallocation is ordered behind the launches of ITS stream only (a launch
+// on another stream waits for the fill through seed_event, but nothing makes a refill wait for readers on other streams).
+inline const ulonglong2 *seed_table(psdr_scene_s *h, const psdr_render_opts *o, long long WH, int nsp, long long n, hipStream_t s) {
+    if (h->opt.seed_cache == 0 || n <= 0 || n > (1ll << std::max(0, std::min(40, h->opt.seed_cache_log2)))) return nullptr;
+    const long long key[4] = {WH, (long long) o->spp, (long long) o->spp_begin, (long long) nsp};
+    if (h->d_seed != nullptr && h->seed_valid && std::equal(key, key + 4, h->seed_key)) {
+        // filled on another stream: this one waits for the fill (on the device)
+        if (s != h->seed_stream && h->seed_event != nullptr && hipStreamWaitEvent(s, h->seed_event, 0) != hipSuccess) { (void) hipGetLastError(); return nullptr; }
+        return reinterpret_cast<const ulonglong2 *>(h->d_seed);
+    }
+    h->seed_valid = false;
+    if ((size_t) n > h->seed_cap) {          // reallocated only when it grows
+        if (h->d_seed) { (void) hipFreeAsync(h->d_seed, s); h->d_seed = nullptr; h->seed_cap = 0; }
+        void *nb = nullptr;
+        if (hipMallocAsync(&nb, (size_t) n * sizeof(ulonglong2), s) != hipSuccess) { (void) hipGetLastError(); return nullptr; }
+        h->d_seed = nb; h->seed_cap = (size_t) n;
+    }
+    if (h->seed_event == nullptr && hipEventCreateWithFlags(&h->seed_event, hipEventDisableTiming) != hipSuccess) { (void) hipGetLastError(); h->seed_event = nullptr; return nullptr; }
+    hipLaunchKernelGGL(k_seed_fill, dim3((unsigned) ((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, reinterpret_cast<ulonglong2 *>(h->d_seed), n, o->spp, o->spp_begin, SlotDiv(nsp));
+    if (hipGetLastError() != hipSuccess || hipEventRecord(h->seed_event, s) != hipSuccess) { (void) hipGetLastError(); return nullptr; }
+    std::copy(key, key + 4, h->seed_key);
+    h->seed_valid = true; h->seed_stream = s; h->seed_fills++;
+    return reinterpret_cast<const ulonglong2 *>(h->d_seed);
+}
+// the instance with a seeded twin: renderC of the PathTracer on a scene without a tree (C2: 816 -> 766 us).  The log-derivative kernel has none: at 80 VGPRs its register
+// allocation does not survive the change ("Seed table").  Everywhere else (trees, geometry duals, reverse mode, edge terms, wavefront stages) a slot's rays
+// dwarf the 168 instructions and an instance costs library size
+template <class G, class R, int FL> constexpr bool seeded_render_c() { return (FL & kSceneTiny) != 0 && (FL & kScenePre) == 0 && std::is_same<G, float>::value && std::is_same<R, float>::value; }
 template <class G, class R, int FL>
 int run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, float *img, float *dimg, hipStream_t s) {
     const long long WH = (long long) h->desc.width * h->desc.height;
@@ -1794,6 +1859,18 @@ int run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, 
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera<G, R, INTEG, FL, NOTREE>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, o->spp, \
                        o->spp_begin, nsp, n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, 0ll, ProbeView{nullptr, nullptr}, own)
 #define PSDR_LAUNCH_CAMERA(INTEG) PSDR_LAUNCH_CAMERA_T(INTEG, ((FL & kSceneTiny) != 0))
+    // renderC of the PathTracer on a scene without a tree: the seeded twin where the handle's seed table serves the launch
+    if constexpr (seeded_render_c<G, R, FL>()) {
+        if (o->integrator == PSDR_INTEGRATOR_PATH) {
+            if (const ulonglong2 *seed = seed_table(h, o, WH, nsp, n, s)) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera_seeded<G, R, PSDR_INTEGRATOR_PATH, FL, true>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv,
+                                   o->spp, o->spp_begin, SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own, seed);
+                HIP_TRY(hipGetLastError());
+                h->seed_launches++;
+                return 0;
+            }
+        }
+    }
     // scenes without a tree are served by their own flag sets (kSceneTiny): occupancy follows from FL alone
     switch (o->integrator) {
         case PSDR_INTEGRATOR_DIRECT: PSDR_LAUNCH_CAMERA(PSDR_INTEGRATOR_DIRECT); break;

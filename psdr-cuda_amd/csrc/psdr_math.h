@@ -235,13 +235,17 @@ struct Rng {
     PSDR_HD static float __uint_as_float_hd(uint32_t b) {
         union { uint32_t u; float f; } c; c.u = b; return c.f;
     }
-    PSDR_HD void init(uint64_t slot, const RngJump &j) {
+    // seed(slot): the stream of a sample slot at its first draw -- a function of the slot id alone (what the seed table of a scene handle
+    // holds, psdr_kernels.h k_seed_fill); apply(jump): the state after the call's rng_offset earlier draws
+    PSDR_HD void seed(uint64_t slot) {
         const uint64_t sv = slot + 0x853c49e6748fea9bull;      // PCG32_DEFAULT_STATE, sampler.h:35
         const uint64_t initstate = tea64(sv, slot), initseq = tea64(slot, sv);
         state = 0; inc = (initseq << 1u) | 1u;
         next_u32(); state += initstate; next_u32();
-        state = j.mult * state + inc * j.plus_unit;
     }
+    PSDR_HD void apply(const RngJump &j) { state = j.mult * state + inc * j.plus_unit; }
+    PSDR_HD void init(uint64_t slot, const RngJump &j) { seed(slot); apply(j); }
+    PSDR_HD void init_seeded(uint64_t seeded_state, uint64_t seeded_inc, const RngJump &j) { state = seeded_state; inc = seeded_inc; apply(j); }
 };
 // (mult, plus_unit) for a jump of `delta` draws (pcg32 advance with inc = 1), on the device too (log2(delta) steps)
 PSDR_HD RngJump rng_jump_hd(uint64_t delta) {

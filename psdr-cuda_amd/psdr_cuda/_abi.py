@@ -85,7 +85,7 @@ TANGENT_FIELDS = ("tri_info", "texels", "emitter_rad", "cam_to_world", "sec_edge
 HIP_SYMBOLS = (
     "psdr_last_error", "psdr_version", "psdr_abi_struct_sizes", "psdr_scene_create", "psdr_scene_destroy", "psdr_scene_set_option", "psdr_scene_set_tables",
     "psdr_bvh_build", "psdr_bvh_stats", "psdr_scene_info", "psdr_trace", "psdr_render_c", "psdr_render_d_fwd", "psdr_render_d_rev",
-    "psdr_guide_build", "psdr_get_counters", "psdr_scene_rev_layout",
+    "psdr_guide_build", "psdr_get_counters", "psdr_scene_rev_layout", "psdr_scene_seed_info",
     "psdr_geo_world_vertices_fwd", "psdr_geo_world_vertices_rev", "psdr_geo_tri_rows_fwd", "psdr_geo_tri_rows_rev", "psdr_geo_sec_edges_fwd", "psdr_geo_sec_edges_rev", "psdr_geo_prim_edges_fwd", "psdr_geo_prim_edges_rev",
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
     "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
@@ -132,6 +132,7 @@ def load_hip():
     lib.psdr_get_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.psdr_scene_info.argtypes = [vp, C.POINTER(i32)]
     lib.psdr_scene_rev_layout.argtypes = [vp, C.POINTER(i32)]
+    lib.psdr_scene_seed_info.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.psdr_geo_world_vertices_fwd.argtypes = [i32, vp, vp, vp, vp, vp]
     lib.psdr_geo_world_vertices_rev.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
     lib.psdr_geo_tri_rows_fwd.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
@@ -188,6 +189,15 @@ def rev_layout(handle):
     return {"tex_n": out[0], "rad_n": out[1], "env_n": out[2], "hot_rows": out[3], "rep": out[4], "priv_rows": out[5], "priv_regs": out[6],
             "pend_rows": out[7], "launch": REV_LAUNCH_KINDS[out[8]], "pe_reps": out[9], "hot_identity": out[10], "deep_rec": out[11],
             "priv_slot": (out[12], out[13]), "tree_hot_rows": out[14], "pe_sorted": out[15]}
+
+
+def seed_cache_info(handle):
+    """psdr_scene_seed_info as a dict: the handle's seed table (option seed_cache) -- slots it holds seeds for, bytes allocated, fills so far and camera
+    launches served from it so far."""
+    lib = load_hip()
+    out = (C.c_int64 * 4)()
+    check(lib, lib.psdr_scene_seed_info(handle, out))
+    return {"slots": int(out[0]), "bytes": int(out[1]), "fills": int(out[2]), "launches": int(out[3])}
 
 
 def make_opts(integrator=INTEGRATOR_DIRECT, bsdf_samples=1, light_samples=1, max_depth=1, hide_emitters=False,
