@@ -253,6 +253,9 @@ int psdr_scene_destroy(psdr_scene_t h);
    seed_cache (1 default: the fused PathTracer renderC launches on a scene without a tree load the seeded PCG32 state of
    their sample slots from a read-only table on the handle, filled once per (width * height, spp, spp range); 0: every kernel seeds its streams itself; same results
    either way); seed_cache_log2 (the largest launch that table serves, log2 of its slots at 16 bytes each: default 25 = 512 MB; larger launches seed themselves);
+   logd_park (1 default: forward-mode PathTracer launches with ONE tangent set on albedo texels, on a plain diffuse scene without a tree, run the lean twin of the
+   log-derivative kernel, which keeps a path's idle state in per-lane LDS columns instead of scratch memory -- where staged scene + columns fit six workgroups per CU
+   and a forced lds_budget; 0: always the kernel without columns; same results either way);
    trace_wg2 (dense trace kernel as two workgroups per CU: -1 by forest and launch size, 0 never, n > 0 always with stack columns of n entries);
    chunk_log2 (slots per chunk of the chunked launches, 0 = default); blocks_per_cu, camera_blocks, lds_budget, sink_rep, bvh_maxleaf (integers,
    0 = default where that makes sense); bvh_tcost (float).  Unknown names fail.  Options that change the tree take effect at the next psdr_bvh_build. */
@@ -412,6 +415,11 @@ int psdr_scene_rev_layout(psdr_scene_t h, int32_t out[16]);
 /* Seed table of the handle (option seed_cache; diagnostics): out = { [0] slots the table holds seeds for (0: none), [1] bytes allocated,
    [2] fills since the handle was created (one per change of width * height, spp or spp range), [3] camera launches served from the table }. */
 int psdr_scene_seed_info(psdr_scene_t h, int64_t out[4]);
+
+/* Log-derivative camera launches of the handle (options logd, logd_park; diagnostics): out = { [0] launches since the handle was created, [1] those the lean
+   twin ran, [2] those of the lean twin that loaded their seeds from the seed table, [3] dynamic LDS bytes per workgroup of the last lean launch (staged
+   scene + parking columns; 0: none yet) }. */
+int psdr_scene_logd_info(psdr_scene_t h, int64_t out[4]);
 
 /* Counters of the last render call on this handle (host values):
    [0] rays traced, [1] camera slots, [2] primary-edge slots, [3] secondary-edge slots. */

@@ -26,6 +26,7 @@ struct LaunchCtx {
     int32_t off_stack;          // byte offset of the traversal stacks inside the dynamic LDS block
     int32_t off_pathrec;        // reverse mode: per-lane (c_k, f_k) path records behind the stacks
     int32_t off_sink;           // reverse mode: the gradient cache of the workgroup (DeviceSink) behind those
+    int32_t off_park;           // lean log-derivative kernel (psdr_logd_lean.h): per-lane parking columns behind the stacks
 };
 
 static_assert(offsetof(LaunchCtx, sc) == 0, "closest_hit reads SceneView::tiny through the kernel-argument segment pointer: LaunchCtx (SceneView first) must be the first kernel argument");
@@ -174,6 +175,7 @@ struct psdr_scene_options {
     int trace_wg2 = -1;                    // the dense trace kernel as two workgroups per CU: -1 by forest and launch size, 0 never, n > 0 always (stack columns of n entries in LDS)
     int seed_cache = 1;                    // PathTracer renderC launches on a scene without a tree load their PCG32 seeds from the handle's seed table (psdr_kernels.h seed_table); 0: every kernel seeds its streams itself
     int seed_cache_log2 = 25;              // log2 of the largest launch the seed table serves, in slots (16 bytes each: 512 MB)
+    int logd_park = 1;                     // K = 1 log-derivative launches on a plain diffuse scene without a tree run the lean twin, whose idle path state sits in LDS columns (psdr_logd_lean.h); 0: k_camera_logd
     int bvh_maxleaf = 4;                   // host SAH builder: leaf size limit (1..8)
     float bvh_tcost = 2.0f;                //                   cost of a node visit in triangle tests
 };
@@ -281,6 +283,8 @@ struct psdr_scene_s {
     hipStream_t seed_stream = nullptr;     // stream of the fill; seed_event marks its end for launches on other streams
     hipEvent_t seed_event = nullptr;
     long long seed_fills = 0, seed_launches = 0;      // psdr_scene_seed_info
+    long long logd_launches = 0, logd_lean_launches = 0, logd_lean_seeded = 0;      // psdr_scene_logd_info
+    int logd_lean_lds = 0, logd_lean_park = 0;        //   dynamic LDS of the last lean launch: staged scene, parking columns (bytes)
     // wavefront PathTracer: path-state streams + stream counters
     void *d_ws = nullptr;
     size_t ws_bytes = 0;
@@ -354,6 +358,10 @@ const PathSedgeOps *path_sedge_ops_4();
 const PathSedgeOps *path_sedge_ops_6();
 const PathSedgeOps *path_sedge_ops_8();
 const PathSedgeOps *path_sedge_ops_10();
+// The lean twin of the K = 1 log-derivative camera kernel for flag set 8 (psdr_logd_lean.hip): launches it behind the gate kernels of run_camera and
+// sets *ran, or leaves *ran false -- option logd_park 0, or the parking columns do not fit six workgroups per CU (or a forced lds_budget) -- and
+// run_camera launches k_camera_logd.  cx: the launch context of run_camera (off_park is set on a copy).
+int logd_lean_launch_8(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCtx &cx, const psdr::TangentView<1, psdr::kSceneTiny> &tv, float *img, float *dimg, hipStream_t s, bool *ran);
 const VariantOps *variant_ops_0();
 const VariantOps *variant_ops_1();
 const VariantOps *variant_ops_2();

@@ -1785,8 +1785,8 @@ inline const ulonglong2 *seed_table(psdr_scene_s *h, const psdr_render_opts *o, 
     h->seed_valid = true; h->seed_stream = s; h->seed_fills++;
     return reinterpret_cast<const ulonglong2 *>(h->d_seed);
 }
-// the instance with a seeded twin: renderC of the PathTracer on a scene without a tree (C2: 816 -> 766 us).  The log-derivative kernel has none: at 80 VGPRs its register
-// allocation does not survive the change ("Seed table").  Everywhere else (trees, geometry duals, reverse mode, edge terms, wavefront stages) a slot's rays
+// the instance with a seeded twin: renderC of the PathTracer on a scene without a tree (C2: 816 -> 766 us).  k_camera_logd has none: at 80 VGPRs its register
+// allocation does not survive the change ("Seed table"); its lean twin, which parks the path's idle state in LDS, has one (psdr_logd_lean.hip).  Everywhere else (trees, geometry duals, reverse mode, edge terms, wavefront stages) a slot's rays
 // dwarf the 168 instructions and an instance costs library size
 template <class G, class R, int FL> constexpr bool seeded_render_c() { return (FL & kSceneTiny) != 0 && (FL & kScenePre) == 0 && std::is_same<G, float>::value && std::is_same<R, float>::value; }
 template <class G, class R, int FL>
@@ -1849,9 +1849,14 @@ int run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, 
             for (int k = 0; k < K; ++k) tvk.t[k] = tv.t[k];
             hipLaunchKernelGGL(k_logd_check<K>, dim3((unsigned) ((h->desc.num_texels + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, h->desc.texels, tvk, h->desc.num_texels, h->d_counters, bad);
             hipLaunchKernelGGL(k_logd_gate, dim3(1), dim3(64), 0, s, h->d_counters, bad);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera_logd<K, FL, ((FL & kSceneTiny) != 0)>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv,
-                               o->spp, o->spp_begin, SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
+            // K = 1 on a plain diffuse scene without a tree (the headline's renderD): the lean twin, where its parking columns fit (psdr_logd_lean.hip)
+            bool lean = false;
+            if constexpr (K == 1 && FL == kSceneTiny) { if (int rc = logd_lean_launch_8(h, o, cx, tv, img, dimg, s, &lean)) return rc; }
+            if (!lean)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera_logd<K, FL, ((FL & kSceneTiny) != 0)>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv,
+                                   o->spp, o->spp_begin, SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
             HIP_TRY(hipGetLastError());
+            h->logd_launches++;
             gated = true;
         }
     }
