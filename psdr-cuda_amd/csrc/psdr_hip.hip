@@ -1174,9 +1174,17 @@ static void update_emit_rows(psdr_scene_s *h) {
     }
     h->emit_rows = h->n_tiny > 0 ? tiny_emitter_rows(h->tiny_meta, h->n_tiny, h->aa_cnt, is_em) : 0u;
 }
+static int bvh_build_or_refit(psdr_scene_s *h, hipStream_t s);
+// A build that returns an error has usually written part of the new tree over the old one already (lbvh_build: the leaf records and the children,
+// before it learns of a non-finite vertex; the host paths: whatever was copied up before a later step failed) while the host-side fields still
+// describe the previous tree: the handle is left WITHOUT a tree -- the next launch is refused, the next build is a full one.
 int psdr_bvh_build(psdr_scene_t h, void *stream) {
     if (!h || !h->have_tables) return fail("Scene not loaded yet!");
-    hipStream_t s = (hipStream_t) stream;
+    const int rc = bvh_build_or_refit(h, (hipStream_t) stream);
+    if (rc) { h->have_bvh = false; h->refit_ok = false; }
+    return rc;
+}
+static int bvh_build_or_refit(psdr_scene_s *h, hipStream_t s) {
     const int T = h->desc.num_tris;
     h->kept.valid = false;                  // records of a value sweep belong to the tree they were traced with
     // ---- refit: same triangle count as the tree on the device and the tree has not degraded
