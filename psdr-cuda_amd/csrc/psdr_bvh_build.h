@@ -500,6 +500,61 @@ inline void collapse_bvh4(const std::vector<BvhNode> &nodes, const std::vector<i
     for (int32_t r : out.roots) if (r >= 0) out.stack_need = std::max(out.stack_need, need[(size_t) r]);
 }
 
+// ------------------------------------------------------------------------ 4-wide tree (boxes)
+// One 4-wide node from the boxes of its (up to) four children (bit c of `valid`: slot c is in use): quantised to 8 bits per plane relative to
+// their union -- origin = lower corner, per-axis scale 2^(E - 127) with 255 * 2^(E - 127) >= extent, lower planes rounded down, upper planes
+// rounded up, so that the dequantised plane fmaf(q, 2^(E - 127), org) never cuts into a child's box; an empty slot has its lower plane (255)
+// above its upper plane (0).  Every operation is exact or correctly rounded on both sides (frexpf, floorf, ceilf, fmaf, powers of two): the
+// device (psdr_hip.hip k_bvh4_fill, after every build and refit of the BVH2) and the host (tests, tools) produce the same bits.
+PSDR_HD Bvh4Node quantise_bvh4(const float lo[4][3], const float hi[4][3], const int32_t child[4], uint32_t valid) {
+    Bvh4Node n;
+    float org[3] = {INFINITY, INFINITY, INFINITY}, top[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int c = 0; c < 4; ++c) {
+        n.child[c] = child[c];
+        if (!((valid >> c) & 1u)) continue;
+        for (int a = 0; a < 3; ++a) { org[a] = fminf(org[a], lo[c][a]); top[a] = fmaxf(top[a], hi[c][a]); }
+    }
+    n.exps = 0; n.pad[0] = n.pad[1] = 0;
+    for (int a = 0; a < 3; ++a) {
+        n.org[a] = org[a];
+        n.qlo[a] = 0xffffffffu; n.qhi[a] = 0u;               // empty slots: lower plane above the upper one
+        const float ext = top[a] - org[a];
+        int e = 0;
+        (void) frexpf(ext * (1.f / 255.f), &e);               // ext / 255 = m * 2^e, m in [0.5, 1): 255 * 2^e >= ext
+        int E = e + 127 < 1 ? 1 : (e + 127 > 254 ? 254 : e + 127);
+        for (;;) {
+            const float scale = __builtin_bit_cast(float, E << 23), inv = 1.f / scale;
+            uint32_t ql = 0, qh = 0; bool ok = true;
+            for (int c = 0; c < 4; ++c) {
+                if (!((valid >> c) & 1u)) { ql |= 0xffu << (8 * c); continue; }
+                int l = (int) floorf((lo[c][a] - org[a]) * inv), u = (int) ceilf((hi[c][a] - org[a]) * inv);
+                l = l > 255 ? 255 : (l < 0 ? 0 : l);
+                while (l > 0 && fmaf((float) l, scale, org[a]) > lo[c][a]) --l;                   // the dequantised plane must not cut into the box
+                while (u <= 255 && fmaf((float) u, scale, org[a]) < hi[c][a]) ++u;
+                if (u > 255) { ok = false; break; }
+                ql |= (uint32_t) l << (8 * c); qh |= (uint32_t) (u < 0 ? 0 : u) << (8 * c);
+            }
+            if (ok || E >= 254) { n.qlo[a] = ql; n.qhi[a] = qh; break; }
+            ++E;
+        }
+        n.exps |= (uint32_t) E << (8 * a);
+    }
+    return n;
+}
+// the node of slot row i of a topology (child / src as collapse_bvh4 leaves them), boxes from the BVH2 nodes
+PSDR_HD Bvh4Node bvh4_node_of(const BvhNode *nodes, const int32_t *child, const int32_t *src) {
+    float lo[4][3], hi[4][3];
+    uint32_t valid = 0u;
+    for (int c = 0; c < 4; ++c) {
+        const int32_t s = src[c];
+        if (s < 0) continue;
+        valid |= 1u << c;
+        const BvhNode &b = nodes[s >> 1];
+        for (int a = 0; a < 3; ++a) { lo[c][a] = (s & 1) ? b.lo1[a] : b.lo0[a]; hi[c][a] = (s & 1) ? b.hi1[a] : b.hi0[a]; }
+    }
+    return quantise_bvh4(lo, hi, child, valid);
+}
+
 // ------------------------------------------------------------------- two-level tree (forest)
 // Scenes made of a few small meshes (walls, lights) and a few large ones (objects): every mesh with at least
 // kMinBlasTris triangles gets its OWN tree; the triangles of the others stay "inline" (tested by every ray in a

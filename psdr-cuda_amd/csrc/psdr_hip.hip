@@ -321,50 +321,13 @@ __global__ void k_gather_top(float4 *__restrict__ top, const BvhNode *__restrict
 
 // ------------------------------------------------------------------------ 4-wide tree (boxes)
 // One thread per 4-wide node: the boxes of its (up to) four children -- each stored in a BVH2 node (src = 2 * node + side) -- are
-// quantised to 8 bits per plane relative to their union: origin = lower corner, per-axis scale 2^e with 255 * 2^e >= extent, lower planes
-// rounded down, upper planes rounded up.  Runs after every build and refit of the BVH2 (a pure function of its boxes).
+// quantised to 8 bits per plane relative to their union (psdr_bvh_build.h quantise_bvh4, shared with the host tests and tools).  Runs after
+// every build and refit of the BVH2 (a pure function of its boxes).
 __global__ __launch_bounds__(kBlock) void k_bvh4_fill(Bvh4Node *__restrict__ out, const BvhNode *__restrict__ nodes, const int32_t *__restrict__ child,
                                                       const int32_t *__restrict__ src, int n4) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n4) return;
-    float lo[4][3], hi[4][3], org[3] = {INFINITY, INFINITY, INFINITY}, top[3] = {-INFINITY, -INFINITY, -INFINITY};
-    Bvh4Node n;
-    for (int c = 0; c < 4; ++c) {
-        n.child[c] = child[(size_t) i * 4 + c];
-        const int32_t s = src[(size_t) i * 4 + c];
-        if (s < 0) continue;
-        const BvhNode &b = nodes[s >> 1];
-        for (int a = 0; a < 3; ++a) {
-            lo[c][a] = (s & 1) ? b.lo1[a] : b.lo0[a]; hi[c][a] = (s & 1) ? b.hi1[a] : b.hi0[a];
-            org[a] = fminf(org[a], lo[c][a]); top[a] = fmaxf(top[a], hi[c][a]);
-        }
-    }
-    n.exps = 0; n.pad[0] = n.pad[1] = 0;
-    for (int a = 0; a < 3; ++a) {
-        n.org[a] = org[a];
-        n.qlo[a] = 0xffffffffu; n.qhi[a] = 0u;               // empty slots: lower plane above the upper one
-        const float ext = top[a] - org[a];
-        int e = 0;
-        (void) frexpf(ext * (1.f / 255.f), &e);               // ext / 255 = m * 2^e, m in [0.5, 1): 255 * 2^e >= ext
-        int E = min(max(e + 127, 1), 254);
-        for (;;) {
-            const float scale = __int_as_float(E << 23), inv = 1.f / scale;
-            uint32_t ql = 0, qh = 0; bool ok = true;
-            for (int c = 0; c < 4; ++c) {
-                if (src[(size_t) i * 4 + c] < 0) { ql |= 0xffu << (8 * c); continue; }
-                int l = (int) floorf((lo[c][a] - org[a]) * inv), u = (int) ceilf((hi[c][a] - org[a]) * inv);
-                l = max(min(l, 255), 0);
-                while (l > 0 && fmaf((float) l, scale, org[a]) > lo[c][a]) --l;                   // the dequantised plane must not cut into the box
-                while (u <= 255 && fmaf((float) u, scale, org[a]) < hi[c][a]) ++u;
-                if (u > 255) { ok = false; break; }
-                ql |= (uint32_t) l << (8 * c); qh |= (uint32_t) max(u, 0) << (8 * c);
-            }
-            if (ok || E >= 254) { n.qlo[a] = ql; n.qhi[a] = qh; break; }
-            ++E;
-        }
-        n.exps |= (uint32_t) E << (8 * a);
-    }
-    out[i] = n;
+    out[i] = bvh4_node_of(nodes, child + (size_t) i * 4, src + (size_t) i * 4);          // psdr_bvh_build.h quantise_bvh4
 }
 
 // --------------------------------------------------------------------- primary-edge slot order

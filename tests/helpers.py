@@ -103,7 +103,7 @@ def hostcheck_lib():
         d = os.path.join(ROOT, "tests", "hostcheck")
         so = os.path.join(d, "libhostcheck.so")
         src = os.path.join(d, "hostcheck.cpp")
-        hdrs = [os.path.join(ROOT, "psdr-cuda_amd", "csrc", f) for f in ("psdr_math.h", "psdr_device.h", "psdr_bvh_build.h")]
+        hdrs = [os.path.join(ROOT, "psdr-cuda_amd", "csrc", f) for f in ("psdr_math.h", "psdr_device.h", "psdr_bvh_build.h")] + [os.path.join(d, "bvh4_host.h")]
         if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in [src] + hdrs):
             subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread",
                                    src, "-o", so])

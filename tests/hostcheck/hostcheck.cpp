@@ -4,6 +4,7 @@
 // the render path (libpsdr_hip.so) only ever executes these functions inside HIP kernels.
 #include "../../psdr-cuda_amd/csrc/psdr_bvh_build.h"
 #include "../../psdr-cuda_amd/csrc/psdr_reverse.h"
+#include "bvh4_host.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -118,6 +119,14 @@ int hostcheck_occluder_rows(const psdr_scene_desc *d, uint32_t *occ_out, int *ro
         if (((uint32_t) ids >> 16) != 0xffffu) row_of_tri[(uint32_t) ids >> 16] = row_of_prim[(size_t) i];
     }
     return 0;
+}
+
+// the host side of the 4-wide tree (bvh4_host.h; tests/test_bvh4_host.py)
+int hostcheck_bvh4(const float *rows, const int32_t *tri_mesh, int T, int num_meshes, int max_leaf, int forest, int32_t *sizes, BvhNode *nodes_out,
+                   float *btris_out, int32_t *roots2_out, int32_t *roots4_out, int32_t *child_out, int32_t *src_out, Bvh4Node *nodes4_out,
+                   int32_t *inline_out, float *boxes_out) {
+    return bvh4_host(rows, tri_mesh, T, num_meshes, max_leaf, forest, sizes, nodes_out, btris_out, roots2_out, roots4_out, child_out, src_out, nodes4_out,
+                     inline_out, boxes_out);
 }
 
 // mode 0: renderC; mode 1: renderD forward (K = 1), all three terms

@@ -320,9 +320,10 @@ def pair_test(tri_info, o, d, tri):
         return dict(t=t, tol_t=(at + np.abs(t) * b) / D, possible=(pos | neg) & (r[:, 21] > 0))
 
 
-def brute_force(tri_info, o, d, chunk=None):
+def brute_force(tri_info, o, d, chunk=None, exclude=None):
     """Float64 Moeller-Trumbore of every ray against every triangle: per ray the two smallest t >= RayEpsilon with their triangle ids and
-    barycentrics (id -1, t inf where there is none); zero-area faces never hit.
+    barycentrics (id -1, t inf where there is none); zero-area faces never hit.  exclude: [m, 2] triangle ids (or -1) ray k does not see at all
+    (a ray that starts on a secondary edge and ignores the edge's two faces).
 
     The test, with s = o - p0, h = d x e2, q = s x e1:  D = e1.h,  Nu = s.h,  Nv = d.q,  Nt = e2.q,  (u, v, t) = (Nu, Nv, Nt) / D.
     Two passes per chunk of rays.  (1) ALL pairs: D, Nu, Nv as matrix products (each triple product is linear in s = o - p0: D = -d.n with
@@ -365,6 +366,10 @@ def brute_force(tri_info, o, d, chunk=None):
         keep = (Nu >= -amax) & (Nv >= -amax) & (Nu + Nv <= D + 3.0 * amax) & live[None]
         ri, ti = np.nonzero(keep)
         del D, Nu, Nv, sg, keep
+        if exclude is not None:
+            ex = np.asarray(exclude, np.int64)[i0:i0 + chunk]
+            seen = (ti != ex[ri, 0]) & (ti != ex[ri, 1])
+            ri, ti = ri[seen], ti[seen]
         # pass 2: the test itself on what is left
         D, Nu, Nv, Nt, b, au, av, at = _pairs(oo[ri], dd[ri], p0[ti], e1[ti], e2[ti])
         sure = (D - b > 0) & (Nu - au > 0) & (Nv - av > 0) & ((D - b) - (Nu + au) - (Nv + av) > 0) & ((Nt - at) - RAY_EPSILON * (D + b) > 0)
@@ -437,6 +442,38 @@ def ray_set(tri_info, seed=0, m=20_000):
     return np.concatenate([po, ro]), np.concatenate([pd, rd]), np.concatenate([owner, np.full(m, -1, np.int64)])
 
 
+def axis_rays(tri_info, m, seed):
+    """m rays with direction components that are EXACTLY zero (the first half along an axis: two zeros; the second half inside an axis plane: one) and
+    origins that are exact in float32: the reciprocal direction holds infinities, and a slab test multiplies them with (plane - origin), which is
+    0 * inf = NaN wherever a plane passes through the origin's coordinate.  Each ray aims at a grid point a few units beside an interior point of a
+    random live triangle -- never 0 units beside it along an axis the direction is zero in, so that no ray runs inside the plane of a planar
+    family.  Along those axes the origin sits OFF the unit lattice by (13, 29, 7) / 64 of a unit in (x, y, z): the legs of the families' triangles
+    lie on lattice lines, their hypotenuses on x + y = integer, a wall's diagonal on x = y, and the planes of a stack rise by 1/8 and 1/4 per unit -- a ray
+    on the lattice (or a simple fraction off it) would meet an edge every other time."""
+    rng = np.random.default_rng(seed)
+    r = np.asarray(tri_info, np.float64)
+    ids = np.nonzero(np.cross(r[:, 3:6], r[:, 6:9]).any(axis=1))[0]
+    k = ids[rng.integers(0, ids.size, m)]
+    b = rng.dirichlet((1.0, 1.0, 1.0), m)
+    p = np.rint((r[k, 0:3] + b[:, 1:2] * r[k, 3:6] + b[:, 2:3] * r[k, 6:9]) * U)                     # units
+    d = rng.normal(size=(m, 3))
+    axis = rng.integers(0, 3, m)
+    zero = np.zeros((m, 3), bool)
+    half = m // 2
+    zero[:half] = True
+    zero[np.arange(half), axis[:half]] = False                   # along `axis`
+    zero[np.arange(half, m), axis[half:]] = True                 # inside the plane normal to `axis`
+    d[zero] = 0.0
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    beside = rng.integers(1, 4, (m, 3)) * rng.choice([-1, 1], (m, 3))
+    aim = p + np.where(zero, beside, rng.integers(-3, 4, (m, 3)))
+    o = np.rint(aim - d * (rng.uniform(0.5, 8.0, (m, 1)) * U))
+    o[zero] = (aim + np.array([13.0, 29.0, 7.0]) / 64)[zero]
+    o, d = (o / U).astype(np.float32), d.astype(np.float32)
+    assert np.array_equal(o.astype(np.float64) * U * 64, np.rint(o.astype(np.float64) * U * 64)) and ((d == 0).sum(1) >= 1).all() and ((d == 0).sum(1)[:half] == 2).all()
+    return o, d
+
+
 def permuted_rows(tri_info, seed):
     """The refit input: every triangle translated to the place of another (a random permutation of the centroids), on the grid -- the
     translation is rounded to whole units, so the moved rows are still exact.  Returns the new p0 columns."""
@@ -495,3 +532,183 @@ def moved(c):
         rays = ray_set(rows, seed=100 + len(c.name))
         _moved[c.name] = (rows, rays, brute_force(rows, rays[0], rays[1]))
     return _moved[c.name]
+
+
+# ---------------------------------------------------------------- two-level scenes (forests): tests/test_bvh4_host.py
+def make_forest_scene(meshes):
+    """Several soups as the meshes of one psdr_cuda.Scene (face normals, no edge lists), all diffuse grey; nothing emits (the tables serve tree
+    builds and ray queries, not renders)."""
+    import psdr_cuda
+    from psdr_cuda.scene import look_at
+    sc = psdr_cuda.Scene()
+    sc.opts.width = sc.opts.height = 8
+    sc.opts.spp, sc.opts.sppe, sc.opts.sppse, sc.opts.log_level = 1, 0, 0, 0
+    cam = psdr_cuda.PerspectiveCamera(40.0, 0.01, 1e4)
+    cam.to_world = look_at([6.0, 5.0, 9.0], [0.5, 0.5, 0.5], [0, 1, 0])
+    sc.add_sensor(cam)
+    grey = psdr_cuda.Diffuse([0.5, 0.6, 0.7]); grey.id = "grey"
+    sc.add_bsdf(grey)
+    for verts, faces in meshes:
+        m = psdr_cuda.Mesh()
+        m.use_face_normals = True
+        m.enable_edges = False
+        m.set_geometry(np.asarray(verts, np.float32), np.asarray(faces, np.int32))
+        sc.add_mesh(m, grey)
+    sc.finalize()
+    sc.configure()
+    return sc
+
+
+def _submesh(verts, faces):
+    """the faces as a mesh of their own (its own vertex array, in face order)"""
+    return np.asarray(verts)[np.asarray(faces).reshape(-1)], np.arange(3 * len(faces), dtype=np.int32).reshape(-1, 3)
+
+
+ROOM_LO, ROOM_HI = -1.0, 1025.0
+
+
+def _room_walls():
+    """six axis-aligned rectangles (12 triangles, fan-triangulated) on the faces of [ROOM_LO, ROOM_HI]^3"""
+    verts, faces = [], []
+    for axis in range(3):
+        a, b = [k for k in range(3) if k != axis]
+        for side in (ROOM_LO, ROOM_HI):
+            c = np.full((4, 3), side)
+            c[:, a] = [ROOM_LO, ROOM_HI, ROOM_HI, ROOM_LO]
+            c[:, b] = [ROOM_LO, ROOM_LO, ROOM_HI, ROOM_HI]
+            n = len(verts)
+            verts.extend(c)
+            faces.extend([[n, n + 1, n + 2], [n, n + 2, n + 3]])
+    return np.asarray(verts, np.float32), np.asarray(faces, np.int32)
+
+
+def forest_meshes(name):
+    """The meshes of a forest input, and which of them the forest builder is meant to give a tree (None: a single tree serves the table).
+      single:<family>  the family as one mesh: one tree, nothing inline
+      overlap16        the first 1034 triangles of uniform_5000: triangle i < 1024 in mesh i % 16 (16 overlapping trees of exactly 64 triangles:
+                       kMaxBlas and kMinBlasTris at once), the last 10 a 17th, inline mesh
+      overlap17        17 x 64 likewise: one tree too many, the table gets the single tree
+      room             12 wall triangles around two_clusters, each cluster a mesh: two trees with disjoint boxes, the walls inline"""
+    if name.startswith("single:"):
+        return [FAMILIES[name[7:]]()], [0]
+    if name in ("overlap16", "overlap17"):
+        k = 16 if name == "overlap16" else 17
+        verts, faces = uniform(5000)
+        meshes = [_submesh(verts, faces[i:64 * k:k]) for i in range(k)]
+        if k == 16:
+            meshes.append(_submesh(verts, faces[1024:1034]))
+        return meshes, (list(range(16)) if k == 16 else None)
+    if name == "room":
+        verts, faces = two_clusters()
+        near = verts[faces].mean(axis=1).max(axis=1) < 512
+        return [_room_walls(), _submesh(verts, faces[near]), _submesh(verts, faces[~near])], [1, 2]
+    raise KeyError(name)
+
+
+FOREST_INPUTS = ["single:" + n for n in ("ladder_R38", "one_cell_1001", "two_clusters", "runs", "planar_x", "planar_y", "planar_z", "with_degenerates",
+                                         "uniform_5000")] + ["overlap16", "overlap17", "room"]
+_forest = {}
+
+
+class ForestCase:
+    """meshes, the tables of the scene (tb), the table rows, the
+    mask of the triangles that are meant to sit in a tree, and -- on first use -- the ray set (the family's own + axis_rays), its brute force over the
+    whole table (bf) and over the tree triangles alone (bf_tree: what a walk of the trees alone, such as the dense trace kernel's, answers)."""
+    def __init__(self, name):
+        self.name = name
+        self.meshes, self.tree_meshes = forest_meshes(name)
+        self._tb = None
+        self.family = case(name[7:]) if name.startswith("single:") else None
+        if self.family is not None:
+            self._tb = self.family.tb
+        self.rows = table_rows(self.tb)
+        mesh_of = (self.tb["tri_mesh"].detach().cpu().numpy() & ~0x40000000)
+        self.mesh_of = mesh_of
+        self.in_tree = np.isin(mesh_of, self.tree_meshes) if self.tree_meshes is not None else np.zeros(mesh_of.shape, bool)
+        self._rays = self._bf = self._bf_tree = None
+
+    @property
+    def tb(self):
+        if self._tb is None:
+            self._tb = make_forest_scene(self.meshes).tables(0)
+        return self._tb
+
+    @property
+    def rays(self):
+        if self._rays is None:
+            seed = len(self.name)
+            ao, ad = axis_rays(self.rows, 2000, seed + 500)
+            if self.family is not None:
+                o, d, owner = self.family.rays
+            else:
+                o, d, owner = ray_set(self.rows, seed=seed)
+            o, d, owner = np.concatenate([o, ao]), np.concatenate([d, ad]), np.concatenate([owner, np.full(2000, -1, np.int64)])
+            if self.name == "room":                                  # rays start inside the room
+                o = np.clip(o, ROOM_LO + 0.25, ROOM_HI - 0.25)
+            self._rays = (o, d, owner)
+        return self._rays
+
+    @property
+    def bf(self):
+        if self._bf is None:
+            o, d, _ = self.rays
+            if self.family is not None:                              # the family's own rays have their answer already
+                tail = brute_force(self.rows, o[-2000:], d[-2000:])
+                self._bf = {k: np.concatenate([self.family.bf[k], tail[k]]) for k in tail}
+            else:
+                self._bf = brute_force(self.rows, o, d)
+        return self._bf
+
+    def tree_rows(self, rows=None):
+        """the table with every triangle outside the trees shrunk to a point (zero area: brute_force never hits it); ids stay global"""
+        rows = (self.rows if rows is None else rows).copy()
+        rows[~self.in_tree, 3:9] = 0
+        return rows
+
+    @property
+    def bf_tree(self):
+        if self._bf_tree is None:
+            if self.in_tree.all():
+                self._bf_tree = self.bf
+            else:
+                self._bf_tree = brute_force(self.tree_rows(), self.rays[0], self.rays[1])
+        return self._bf_tree
+
+
+def forest_case(name):
+    if name not in _forest:
+        _forest[name] = ForestCase(name)
+    return _forest[name]
+
+
+_edges = None
+
+
+def edges_case(n_edges=2000):
+    """cbox_bunny's own tables, the only input with sec_edge_faces: rays that start ON n_edges of its secondary edges (midpoint + a random direction),
+    each twice -- first half with its edge index (a walk that ignores the edge's two faces, as the dense trace kernel's IGN instances do), second half with -1 -- and the
+    brute force over the tree triangles with (bf_ign) and without (bf) the two faces removed on the first half."""
+    global _edges
+    if _edges is None:
+        from helpers import load_scene
+        sc, _ = load_scene("cbox_bunny", res=8, spp=1, sppse=1)
+        tb = sc.tables(0)
+        rows = table_rows(tb)
+        mesh_of = tb["tri_mesh"].detach().cpu().numpy() & ~0x40000000
+        in_tree = np.bincount(mesh_of)[mesh_of] >= 64
+        se = tb["sec_edge"].detach().cpu().numpy().astype(np.float64)
+        faces = tb["sec_edge_faces"].detach().cpu().numpy().astype(np.int64)
+        rng = np.random.default_rng(91)
+        own = np.nonzero(in_tree[faces[:, 0]])[0]                    # the bunny's edges, not the walls'
+        pick = own[rng.choice(own.size, min(n_edges, own.size), replace=False)]
+        d = rng.normal(size=(pick.size, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        o = (se[pick, 0:3] + 0.5 * se[pick, 3:6]).astype(np.float32)
+        o, d = np.concatenate([o, o]), np.concatenate([d, d]).astype(np.float32)
+        edge = np.concatenate([pick, np.full(pick.size, -1)]).astype(np.int32)
+        ex = np.concatenate([faces[pick], np.full((pick.size, 2), -1)])
+        tree_rows = rows.copy()
+        tree_rows[~in_tree, 3:9] = 0
+        _edges = dict(tb=tb, rows=rows, in_tree=in_tree, o=o, d=d, edge=edge, faces=faces[pick], bf=brute_force(tree_rows, o, d),
+                      bf_ign=brute_force(tree_rows, o, d, exclude=ex))
+    return _edges

@@ -1,5 +1,5 @@
 // walk_stats.cpp -- developer tool (host only): statistics of the 4-wide walk on the product's own forest (psdr_bvh_build.h ForestBuilder +
-// collapse_bvh4, boxes quantised as csrc/psdr_hip.hip k_bvh4_fill does): node / leaf visits per ray, how deep the traversal stack gets, and
+// collapse_bvh4, boxes quantised by the function csrc/psdr_hip.hip k_bvh4_fill calls): node / leaf visits per ray, how deep the traversal stack gets, and
 // which share of the node visits falls into the first N nodes of the level-ordered array (= what an LDS stage of N nodes would serve).
 #include "../../psdr-cuda_amd/csrc/psdr_bvh_build.h"
 #include <cstdio>
@@ -8,43 +8,7 @@ using namespace psdr;
 
 static void fill4(const std::vector<BvhNode> &nodes, const Bvh4Topology &tp, std::vector<Bvh4Node> &out) {
     out.resize((size_t) tp.n4);
-    for (int i = 0; i < tp.n4; ++i) {
-        float lo[4][3], hi[4][3], org[3] = {INFINITY, INFINITY, INFINITY}, top[3] = {-INFINITY, -INFINITY, -INFINITY};
-        Bvh4Node n{};
-        for (int c = 0; c < 4; ++c) {
-            n.child[c] = tp.child[(size_t) i * 4 + c];
-            const int32_t s = tp.src[(size_t) i * 4 + c];
-            if (s < 0) continue;
-            const BvhNode &b = nodes[(size_t) (s >> 1)];
-            for (int a = 0; a < 3; ++a) {
-                lo[c][a] = (s & 1) ? b.lo1[a] : b.lo0[a]; hi[c][a] = (s & 1) ? b.hi1[a] : b.hi0[a];
-                org[a] = std::min(org[a], lo[c][a]); top[a] = std::max(top[a], hi[c][a]);
-            }
-        }
-        for (int a = 0; a < 3; ++a) {
-            n.org[a] = org[a];
-            int e = 0; (void) std::frexp((top[a] - org[a]) * (1.f / 255.f), &e);
-            int E = std::min(std::max(e + 127, 1), 254);
-            for (;;) {
-                union { int i; float f; } sc; sc.i = E << 23;
-                const float scale = sc.f, inv = 1.f / scale;
-                uint32_t ql = 0, qh = 0; bool ok = true;
-                for (int c = 0; c < 4; ++c) {
-                    if (tp.src[(size_t) i * 4 + c] < 0) { ql |= 0xffu << (8 * c); continue; }
-                    int l = (int) std::floor((lo[c][a] - org[a]) * inv), u = (int) std::ceil((hi[c][a] - org[a]) * inv);
-                    l = std::max(std::min(l, 255), 0);
-                    while (l > 0 && std::fma((float) l, scale, org[a]) > lo[c][a]) --l;
-                    while (u <= 255 && std::fma((float) u, scale, org[a]) < hi[c][a]) ++u;
-                    if (u > 255) { ok = false; break; }
-                    ql |= (uint32_t) l << (8 * c); qh |= (uint32_t) std::max(u, 0) << (8 * c);
-                }
-                if (ok || E >= 254) { n.qlo[a] = ql; n.qhi[a] = qh; break; }
-                ++E;
-            }
-            n.exps |= (uint32_t) E << (8 * a);
-        }
-        out[(size_t) i] = n;
-    }
+    for (int i = 0; i < tp.n4; ++i) out[(size_t) i] = bvh4_node_of(nodes.data(), &tp.child[(size_t) i * 4], &tp.src[(size_t) i * 4]);
 }
 
 struct Stat { int nodes = 0, leaves = 0, tris = 0, max_sp = 0; };
