@@ -182,7 +182,8 @@ typedef struct psdr_scene_desc {
 /* psdr_render_d_fwd / psdr_render_d_rev with PSDR_INTEGRATOR_PATH: evaluate the secondary-edge boundary term of the PathTracer on the slots
    sppse / sppse_begin / sppse_end name (per slot a direct-source and an indirect-source boundary segment, each with a random
    walk of camera connections on the sensor side; max_depth = 1 is DirectIntegrator(1, 1)'s term draw for draw).  A slot of sampler 2 then
-   consumes 11 max_depth - 9 draws (3 at max_depth = 1).  max_depth <= 8; a guiding grid is not supported.  Without the flag a PathTracer call
+   consumes 11 max_depth - 9 draws (3 at max_depth = 1).  max_depth <= 8.  The descriptor's guiding grid guides the direct-source segment, psdr_scene_set_path_guide's the indirect-source segment (a guided
+   slot warps its numbers, it draws no other ones).  Without the flag a PathTracer call
    ignores sppse, as it always did; other integrators ignore the flag.  Scene options pt_sedge (3: both segments, 1: direct source only,
    2: indirect source only, 0: neither) and pt_sedge_walk (0: the walk stops at its first vertex) are A/B switches for tests. */
 #define PSDR_FLAG_PATH_SEDGES 16
@@ -317,6 +318,26 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *opts,
 int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *opts,
                      const int32_t reso[4], int32_t nrounds,
                      float *out_mass, void *stream);
+
+/* Guiding grids of the PathTracer's secondary-edge term (PSDR_FLAG_PATH_SEDGES; no reference counterpart: the
+   snapshot has no PathTracer).  A slot evaluates two boundary segments; each may have a 3-D grid with the semantics
+   of HyperCubeDistribution3f over the three numbers that decide it: segment A (direct source) over the slot's
+   sample3 -- the descriptor's guide_* grid, the very cube of DirectIntegrator's term -- and segment B (indirect
+   source) over (sample3[0], the two sphere-direction numbers).
+
+   psdr_scene_set_path_guide installs segment B's grid on the handle: reso [3], cmf / pmf [reso0*reso1*reso2] and
+   sum as psdr_cube_sample_reuse takes them; the device tables stay the caller's.  cmf == NULL clears the grid.
+   psdr_scene_set_tables drops it (as it replaces every other table): set it again after every set_tables.
+
+   psdr_path_guide_build estimates a grid's mass for segment 1 (A) or 2 (B), unguided (any grid that is set is
+   ignored), with opts->max_depth and the handle's pt_sedge_walk:
+   out_mass [reso0*reso1*reso2] = mean over nrounds of the sum over the cell's reso[3] streams of
+   hmax(sum over the segment's camera connections of |value|) / reso[3].  At max_depth 1 the mass of segment 1 is
+   psdr_guide_build's. */
+int psdr_scene_set_path_guide(psdr_scene_t h, const int32_t reso[3], const float *cmf, const float *pmf, float sum);
+int psdr_path_guide_build(psdr_scene_t h, const psdr_render_opts *opts, int32_t segment,
+                          const int32_t reso[4], int32_t nrounds,
+                          float *out_mass, void *stream);
 
 /* Replaces HyperCubeDistribution<ndim>::sample_reuse (src/core/cube_distrb.cpp:41-48), ndim = 2 or 3:
    samples [m][ndim] are warped IN PLACE, out_pdf [m] = pmf * n.  cmf / pmf / sum as DiscreteDistribution

@@ -1118,6 +1118,17 @@ int psdr_scene_set_tables(psdr_scene_t h, const psdr_scene_desc *desc) {
     // material_mask = 0: unknown -> serve every BSDF type
     h->has_rough = d.material_mask == 0 || (d.material_mask & (1u << PSDR_BSDF_ROUGHCONDUCTOR)) != 0;
     h->have_tables = true;
+    h->pg_cmf = h->pg_pmf = nullptr; h->pg_sum = 0.f;          // segment B's guiding grid belongs to the tables it was built for (psdr_scene_set_path_guide)
+    return 0;
+}
+
+int psdr_scene_set_path_guide(psdr_scene_t h, const int32_t reso[3], const float *cmf, const float *pmf, float sum) {
+    if (!h) return fail("psdr_scene_set_path_guide: null argument");
+    if (!cmf) { h->pg_cmf = h->pg_pmf = nullptr; h->pg_sum = 0.f; return 0; }
+    if (!reso || !pmf) return fail("psdr_scene_set_path_guide: null argument");
+    if (reso[0] <= 0 || reso[1] <= 0 || reso[2] <= 0 || (long long) reso[0] * reso[1] * reso[2] > 0x7fffffffLL) return fail("psdr_scene_set_path_guide: invalid resolution");
+    for (int i = 0; i < 3; ++i) h->pg_reso[i] = reso[i];
+    h->pg_cmf = cmf; h->pg_pmf = pmf; h->pg_sum = sum;
     return 0;
 }
 
@@ -1446,6 +1457,26 @@ int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *o, const int32_t re
     if (n <= 0 || n > 0x7fffffffLL) return fail("psdr_guide_build: invalid resolution");
     HIP_TRY(hipMemsetAsync(out_mass, 0, sizeof(float) * cells, s));
     return variant_of(h)->guide(h, cx, reso, nrounds, n, out_mass, s);
+}
+
+int psdr_path_guide_build(psdr_scene_t h, const psdr_render_opts *o, int32_t segment, const int32_t reso[4], int32_t nrounds, float *out_mass, void *stream) {
+    if (!h || !o || !reso || !out_mass) return fail("psdr_path_guide_build: null argument");
+    if (nrounds <= 0) return fail("psdr_path_guide_build: nrounds must be positive");
+    if (o->integrator != PSDR_INTEGRATOR_PATH) return fail("psdr_path_guide_build: the integrator must be PSDR_INTEGRATOR_PATH");
+    if (o->max_depth < 1) return fail("psdr_path_guide_build: max_depth must be at least 1");
+    if (o->max_depth > PSDR_PATH_SEDGES_MAX_DEPTH) return fail("psdr_path_guide_build: PathTracer max_depth > 8 is not supported for the secondary-edge term");
+    if (segment != 1 && segment != 2) return fail("psdr_path_guide_build: segment must be 1 (direct source) or 2 (indirect source)");
+    if (segment == 2 && o->max_depth < 2) return fail("psdr_path_guide_build: segment 2 needs max_depth >= 2");
+    if (!h->have_tables) return fail("Scene not loaded yet!");
+    if (h->desc.num_sec_edges <= 0) return fail("psdr_path_guide_build: scene has no secondary edges");
+    if (reso[0] <= 0 || reso[1] <= 0 || reso[2] <= 0 || reso[3] <= 0) return fail("psdr_path_guide_build: invalid resolution");
+    const long long cells = (long long) reso[0] * reso[1] * reso[2];
+    if (cells > 0x7fffffffLL || cells * reso[3] > 0x7fffffffLL || cells * reso[3] * (long long) nrounds > 0x7fffffffLL)
+        return fail("psdr_path_guide_build: more than 2^31 (stream, round) slots");
+    hipStream_t s = (hipStream_t) stream;
+    if (int rc = begin_call(h, s)) return rc;
+    HIP_TRY(hipMemsetAsync(out_mass, 0, sizeof(float) * cells, s));
+    return path_sedge_of(h)->guide(h, o, segment, reso, nrounds, out_mass, s);
 }
 
 int psdr_cube_sample_reuse(int32_t ndim, const int32_t *reso, const float *cmf, const float *pmf, float sum, int32_t n, int32_t m, float *samples,

@@ -300,6 +300,11 @@ struct psdr_scene_s {
     // 40.8 -> 35.8, PathTracer(3) renderC 8.0 -> 6.2, PathTracer(3) reverse 25.2 -> 12.8; profiles/r06_bunny_light_forest.txt): default 0 since round 6
     uint32_t emit_rows = 0;                // SceneView::emit_rows of the current tree (psdr_bvh_build)
     int forest_min_inline = 0;
+    // guiding grid of segment B of the PathTracer's secondary-edge term (psdr_scene_set_path_guide; caller-owned device tables, dropped by psdr_scene_set_tables);
+    // segment A's grid is desc.guide_*
+    int32_t pg_reso[3] = {1, 1, 1};
+    const float *pg_cmf = nullptr, *pg_pmf = nullptr;
+    float pg_sum = 0.f;
 };
 
 constexpr int kRayCounters = 64, kRayCounterStride = 16;     // d_counters: 64 counters, 128 bytes apart
@@ -349,6 +354,7 @@ struct VariantOps {
 struct PathSedgeOps {
     int (*fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *dimg, hipStream_t s);
     int (*rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, hipStream_t s);
+    int (*guide)(psdr_scene_s *h, const psdr_render_opts *o, int segment, const int32_t reso[4], int nrounds, float *out_mass, hipStream_t s);      // psdr_path_guide_build
 };
 const PathSedgeOps *path_sedge_ops_0();
 const PathSedgeOps *path_sedge_ops_1();

@@ -10,13 +10,32 @@
 // the camera ray's hit (solid-angle form, as the reference), the connections at y_1.. from the material point of p1 on its triangle (path-space form).
 // The functions are mode-agnostic templates over two callables (the camera connection at y_0 and the sink of a connection's value), so forward mode,
 // reverse mode and the host harness run ONE copy of the estimator.
+//
+// Guiding.  The three numbers that decide a segment before its first ray -- A: s3[0..2] (edge point, emitter sample: DirectIntegrator's draw),
+// B: (s3[0], u, v) (edge point, sphere direction) -- are warped by an optional 3-D grid per segment with the semantics of HyperCubeDistribution3f
+// (cube_sample_reuse<3>), and the returned pdf divides the segment's contribution by the rule of k_secondary_edge (pdf > kEpsilon ? 1 / pdf : 1).  Grid A is
+// the scene descriptor's grid (guide_*), grid B travels in PathSedgeOpts.  The grids are independent: B warps the RAW s3[0], never what grid A made of it.
+// No draw moves: a guided slot warps numbers, it never redraws them.  The template flag G = false compiles the grids out (the kernels of unguided launches: the
+// guided branch cost k_path_sedge_rev<4> its second wave per SIMD); G = true looks at run time, so one host build serves both.
 #pragma once
 #include "psdr_reverse.h"
 
 namespace psdr {
 
 constexpr int kMaxPathSedgeDepth = PSDR_PATH_SEDGES_MAX_DEPTH;              // per-slot source sums live in registers: d - 1 <= 7 entries
-struct PathSedgeOpts { int max_depth, seg, walk; };          // seg: bit 0 = segment A, bit 1 = segment B; walk = 0: the walk stops at y_0
+// the grid of one segment: n = r0 r1 r2 cells, cell (c0, c1, c2) at (c0 r1 + c1) r2 + c2; cmf == nullptr: the segment is not guided
+struct PathGuide { const float *cmf = nullptr, *pmf = nullptr; float sum = 0.f; int n = 0, r0 = 1, r1 = 1, r2 = 1; };
+struct PathSedgeOpts { int max_depth, seg, walk; PathGuide gb = {}; };          // seg: bit 0 = segment A, bit 1 = segment B; walk = 0: the walk stops at y_0; gb: segment B's grid
+// ... as a kernel argument: an unguided launch carries no grid
+template <bool G> struct PathSedgeArgs;
+template <> struct PathSedgeArgs<false> { int max_depth, seg, walk; PSDR_HD PathSedgeOpts opts() const { return PathSedgeOpts{max_depth, seg, walk}; } };
+template <> struct PathSedgeArgs<true> { int max_depth, seg, walk; PathGuide gb; PSDR_HD PathSedgeOpts opts() const { return PathSedgeOpts{max_depth, seg, walk, gb}; } };
+// warps s by the grid and returns what the segment's density is multiplied by (1 where k_secondary_edge's rule leaves the value alone)
+PSDR_HD float path_guide_warp(const PathGuide &g, float s[3]) {
+    const float pdf = cube_sample_reuse<3>(g.cmf, g.pmf, g.sum, g.n, g.r0, g.r1, g.r2, s);
+    return pdf > kEpsilon ? pdf : 1.f;
+}
+PSDR_HD bool guided_a(const SceneView &sc) { return sc.d.guide_cmf != nullptr && sc.d.num_guide_cells > 0; }
 
 // draws of one slot of sampler 2: s3 | 2 direction numbers | 3 (d-1) walk numbers of A | 3 (d-2) of B | 5 (d-1) source-bounce numbers
 PSDR_HD int path_sedge_draws(int d) { return d >= 2 ? 11 * d - 9 : 3; }
@@ -104,13 +123,20 @@ PSDR_HD bool path_sedge_rays_b(const SceneView &sc, TraversalStack &st, const Se
     its1c = intersect<float>(sc, tv0, st, RayT<float>{ep.p0, -dir}, valid, kDetached, nrays, f0, f1);
     return valid && its1c.valid;
 }
-// the filter predicate of segment B in a split launch: the slot's direction draw and its two rays
+// the filter predicate of segment B: the two rays of the segment that (s0, u, v) decide
 template <int FL>
-PSDR_HD bool path_sedge_survives_b(const SceneView &sc, TraversalStack &st, Rng &rng /* after s3 */, float s0, uint32_t &nrays) {
-    const float u = rng.next(), v = rng.next();
+PSDR_HD bool path_sedge_survives_b_at(const SceneView &sc, TraversalStack &st, float s0, float u, float v, uint32_t &nrays) {
     const SedgePoint ep = sedge_point(sc, s0);
     Its<float> its2, its1c;
     return path_sedge_rays_b<FL>(sc, st, ep, uniform_sphere(u, v), its2, its1c, nrays);
+}
+// ... in a split launch: the slot's direction draw, warped by segment B's grid exactly as path_sedge_slot re-derives it for the survivors
+template <int FL>
+PSDR_HD bool path_sedge_survives_b(const SceneView &sc, TraversalStack &st, Rng &rng /* after s3 */, float s0, uint32_t &nrays, const PathGuide *gb = nullptr) {
+    const float u = rng.next(), v = rng.next();
+    float sb[3] = {s0, u, v};
+    if (gb != nullptr && gb->cmf != nullptr) (void) path_guide_warp(*gb, sb);
+    return path_sedge_survives_b_at<FL>(sc, st, sb[0], sb[1], sb[2], nrays);
 }
 
 // What one segment hands to the mode-specific code: the edge, its two hits and the geometry of the boundary
@@ -213,14 +239,16 @@ PSDR_HD Vec3f sedge_dn_vjp(Sink &sink, const SceneView &sc, const Vec3f &x, cons
 
 // Runs both segments of a slot.  begin(seg) -> bool prepares the mode's per-segment state (dn of the material form ..), cam0 / emit as in path_sedge_walk,
 // end(seg) finishes the segment (reverse mode: the two VJP chains).  rng: the slot's stream after s3.  count_first: the slot's first two rays per segment
-// are counted here (false: the filter of a split launch traced and counted them).
-template <int FL, class Begin, class Cam0, class Emit, class End>
+// are counted here (false: the filter of a split launch traced and counted them).  uv: the direction numbers of segment B when they are not the stream's (the
+// guiding-grid build: the cell sample); the stream advances past its two all the same.
+template <int FL, bool G = true, class Begin, class Cam0, class Emit, class End>
 PSDR_HD void path_sedge_slot(const SceneView &sc, TraversalStack &st, Rng rng, const float s3[3], const PathSedgeOpts &po, uint32_t &nrays, bool count_first,
-                             Begin &&begin, Cam0 &&cam0, Emit &&emit, End &&end) {
+                             Begin &&begin, Cam0 &&cam0, Emit &&emit, End &&end, const float *uv = nullptr) {
     const TangentView<0, FL> tv0{};
     const int d = po.max_depth;
     float u = 0.f, v = 0.f;
     if (d >= 2) { u = rng.next(); v = rng.next(); }
+    if (uv != nullptr) { u = uv[0]; v = uv[1]; }
     Rng rng_a = rng, rng_b = rng;
     if (d >= 2) rng_skip(rng_b, 3 * (d - 1));
     Rng rng_s = rng_b;
@@ -232,9 +260,11 @@ PSDR_HD void path_sedge_slot(const SceneView &sc, TraversalStack &st, Rng rng, c
 #pragma unroll
     for (int q = 0; q < kMaxPathSedgeDepth - 1; ++q) P.c[q] = Vec3f(0.f);
     if (po.seg & 1) {
-        const BoundarySeg bs = boundary_segment_direct<FL>(sc, s3);
+        float sa[3] = {s3[0], s3[1], s3[2]}, ga = 1.f;
+        if (G && guided_a(sc)) { const float pdf = guide_sample_reuse(sc, sa); ga = pdf > kEpsilon ? pdf : 1.f; }
+        const BoundarySeg bs = boundary_segment_direct<FL>(sc, sa);
         if (path_sedge_rays_a<FL>(sc, st, bs, sg.dir, sg.its2, sg.its1c, n12)) {
-            sg.k = bs.k; sg.s1 = bs.s1; sg.p0 = bs.p0; sg.bpdf = bs.pdf;
+            sg.k = bs.k; sg.s1 = bs.s1; sg.p0 = bs.p0; sg.bpdf = bs.pdf * ga;
             sedge_geom(sg, bs.edge, bs.edge2, bs.n, bs.p2);
             sg.src_a = Le<float>(sc, tv0, sg.its2, true);
             if (begin(sg)) {
@@ -244,10 +274,12 @@ PSDR_HD void path_sedge_slot(const SceneView &sc, TraversalStack &st, Rng rng, c
         }
     }
     if ((po.seg & 2) && d >= 2) {
-        const SedgePoint ep = sedge_point(sc, s3[0]);
-        sg.dir = uniform_sphere(u, v);
+        float sb[3] = {s3[0], u, v}, gb = 1.f;          // the RAW s3[0]: the grids are independent
+        if (G && po.gb.cmf != nullptr) gb = path_guide_warp(po.gb, sb);
+        const SedgePoint ep = sedge_point(sc, sb[0]);
+        sg.dir = uniform_sphere(sb[1], sb[2]);
         if (path_sedge_rays_b<FL>(sc, st, ep, sg.dir, sg.its2, sg.its1c, n12)) {
-            sg.k = ep.k; sg.s1 = ep.s1; sg.p0 = ep.p0; sg.bpdf = ep.pdf_len * 0.07957747154594767f;          // density of (edge point, direction): 1 / (4 pi) per solid angle
+            sg.k = ep.k; sg.s1 = ep.s1; sg.p0 = ep.p0; sg.bpdf = ep.pdf_len * 0.07957747154594767f * gb;          // density of (edge point, direction): 1 / (4 pi) per solid angle, times the grid's
             sedge_geom(sg, ep.edge, ep.edge2, sg.its2.n, sg.its2.p);
             sg.src_a = Vec3f(0.f);
             if (sg.geom_ok) {
@@ -263,7 +295,7 @@ PSDR_HD void path_sedge_slot(const SceneView &sc, TraversalStack &st, Rng rng, c
 }
 
 // ---- forward mode: out(pixel, value) receives one connection's tangent-only value (R = Dual<K>), to be scaled and added to the derivative image
-template <class R, class TVT, class Out>
+template <class R, bool G = true, class TVT, class Out>
 PSDR_HD void path_secondary_edge_sample(const SceneView &sc, const TVT &tv, TraversalStack &st, const Rng &rng, const float s3[3], const PathSedgeOpts &po, uint32_t &nrays,
                                         bool count_first, Out &&out) {
     constexpr int FL = TVT::flags;
@@ -299,11 +331,11 @@ PSDR_HD void path_secondary_edge_sample(const SceneView &sc, const TVT &tv, Trav
         out(pixel, zero_nonfinite(res - detach(res)));
     };
     auto end = [&](const SedgeSegment &) {};
-    path_sedge_slot<FL>(sc, st, rng, s3, po, nrays, count_first, begin, cam0, emit, end);
+    path_sedge_slot<FL, G>(sc, st, rng, s3, po, nrays, count_first, begin, cam0, emit, end);
 }
 
 // ---- reverse mode: the connections of one segment add <adj_pixel, value> into one seed per form; the VJP chain of dn then runs once per form
-template <class Sink>
+template <bool G = true, class Sink>
 PSDR_HD void path_secondary_edge_reverse(Sink &sink, const SceneView &sc, TraversalStack &st, const Rng &rng, const float s3[3], const PathSedgeOpts &po, float scale,
                                          const float *__restrict__ adj_img, uint32_t &nrays, bool count_first) {
     constexpr int FL = Sink::flags;
@@ -361,7 +393,34 @@ PSDR_HD void path_secondary_edge_reverse(Sink &sink, const SceneView &sc, Traver
             scatter_vec(sink, sg.its1c.tri, 0, a_x); scatter_vec(sink, sg.its1c.tri, 3, a_x * sg.its1c.hu); scatter_vec(sink, sg.its1c.tri, 6, a_x * sg.its1c.hv);
         }
     };
-    path_sedge_slot<FL>(sc, st, rng, s3, po, nrays, count_first, begin, cam0, emit, end);
+    path_sedge_slot<FL, G>(sc, st, rng, s3, po, nrays, count_first, begin, cam0, emit, end);
+}
+
+// ---- guiding-grid build (psdr_path_guide_build): what ONE unguided evaluation of segment po.seg (1 = A, 2 = B) adds to its cell before the division by the
+// streams per cell and the rounds: hmax over the colour channels of the sum over the segment's camera connections of |value0|.  c3: the cell sample -- s3 of
+// segment A, (s3[0], u, v) of segment B; rest: the stream of every other number of the evaluation, laid out as a render slot's stream after s3 (its two direction
+// numbers are skipped).  The caller's scene view carries no grid and po.gb is empty: like psdr_guide_build, the build ignores any grid that is set.
+template <int FL>
+PSDR_HD float path_sedge_mass(const SceneView &sc, TraversalStack &st, const Rng &rest, const float c3[3], const PathSedgeOpts &po, uint32_t &nrays, bool count_first) {
+    const TangentView<0, FL> tv0{};
+    Vec3f acc(0.f);
+    const SedgeSegment *cur = nullptr;
+    auto begin = [&](const SedgeSegment &sg) { cur = &sg; return true; };
+    auto cam0 = [&](float qx, float qy, Vec3f &d0, int &tri) {
+        const RayT<float> cam = primary_ray<float>(sc, tv0, qx, qy);
+        const Its<float> its1 = intersect<float>(sc, tv0, st, cam, true, kDetached, nrays);
+        if (!its1.valid) return false;
+        if (sc.literal_forms && !(norm(its1.p - cur->its1c.p) < kShadowEpsilon)) return false;
+        d0 = -cam.d; tri = its1.tri;
+        return true;
+    };
+    auto emit = [&](int, int, const Vec3f &value0) {
+        const Vec3f v = zero_nonfinite(value0);
+        acc = acc + Vec3f{fabsf(v.x), fabsf(v.y), fabsf(v.z)};
+    };
+    auto end = [&](const SedgeSegment &) {};
+    path_sedge_slot<FL, false>(sc, st, rest, c3, po, nrays, count_first, begin, cam0, emit, end, po.seg == 2 ? c3 + 1 : nullptr);
+    return fmaxf(acc.x, fmaxf(acc.y, acc.z));
 }
 
 }  // namespace psdr

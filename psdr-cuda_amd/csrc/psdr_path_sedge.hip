@@ -33,44 +33,98 @@ namespace {
 // first two rays for most slots, and a survivor then runs up to d-1 walk bounces (and, segment B, up to d-1 source bounces).  Split launch: per segment a
 // filter over all slots (k_secondary_edge_filter for segment A: the very predicate of DirectIntegrator's term; k_path_sedge_filter for segment B), then this
 // kernel over the compacted survivor list with po.seg naming the one segment the list belongs to.  Small launches run it once over all slots, both segments.
-template <int FL>
-__global__ __launch_bounds__(kBlock, 4) void k_path_sedge_filter(LaunchCtx cx, long long i0, long long n, uint32_t *__restrict__ list, int *__restrict__ list_n, unsigned long long *counters) {
+// Guided slots (psdr_path_sedge.h): segment A's grid is the descriptor's, which k_secondary_edge_filter warps by already; segment B's arrives as an argument of
+// k_path_sedge_filter_g and in PathSedgeArgs<true> of the survivor kernels, which repeat the warp.  A launch with either grid runs the G = true instances; the
+// G = false ones are the unguided kernels, compiled without the branch.
+template <int FL, class Keep>
+__device__ __forceinline__ void path_sedge_filter_loop(const LaunchCtx &cx, long long n, uint32_t *__restrict__ list, int *__restrict__ list_n, unsigned long long *counters, Keep &&keep_slot) {
     TraversalStack st; setup_lds(cx, st);
     uint32_t nrays = 0;
     const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
     const int lane = threadIdx.x & 63;
     for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
         bool keep = false;
-        if (j < n) {
-            Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
-            const float s0 = rng.next();
-            (void) rng.next(); (void) rng.next();
-            keep = path_sedge_survives_b<FL>(cx.sc, st, rng, s0, nrays);
-        }
+        if (j < n) keep = keep_slot(st, j, nrays);
         // (one atomic per wave and trip -- not the per-wave LDS buffer of k_secondary_edge_filter: 6-9 % of the slots pass this predicate, nearly every wave appends)
         const unsigned long long mask = __ballot(keep);
         if (mask != 0ull) {
             int base = 0;
             if (lane == 0) base = atomicAdd(list_n, (int) __popcll(mask));
             base = __shfl(base, 0, 64);
-            if (keep) list[base + (int) __popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t) j;
+            if (keep) list[base + (int) __popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t) j;          // base + rank < n: a slot appends at most once
         }
     }
     count_rays(counters, nrays);
 }
+template <int FL>
+__global__ __launch_bounds__(kBlock, 4) void k_path_sedge_filter(LaunchCtx cx, long long i0, long long n, uint32_t *__restrict__ list, int *__restrict__ list_n, unsigned long long *counters) {
+    path_sedge_filter_loop<FL>(cx, n, list, list_n, counters, [&](TraversalStack &st, long long j, uint32_t &nrays) {
+        Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
+        const float s0 = rng.next();
+        (void) rng.next(); (void) rng.next();
+        return path_sedge_survives_b<FL>(cx.sc, st, rng, s0, nrays);
+    });
+}
+// ... of a launch with a grid on segment B: the warp of path_sedge_slot
+template <int FL>
+__global__ __launch_bounds__(kBlock, 4) void k_path_sedge_filter_g(LaunchCtx cx, long long i0, long long n, uint32_t *__restrict__ list, int *__restrict__ list_n, unsigned long long *counters,
+                                                                    PathGuide gb) {
+    path_sedge_filter_loop<FL>(cx, n, list, list_n, counters, [&](TraversalStack &st, long long j, uint32_t &nrays) {
+        Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
+        const float s0 = rng.next();
+        (void) rng.next(); (void) rng.next();
+        return path_sedge_survives_b<FL>(cx.sc, st, rng, s0, nrays, &gb);
+    });
+}
 
-template <int K, int FL>
+// ---------------------------------------------------------------------- guiding-grid build (psdr_path_guide_build)
+// Slot j = (round r = j / gg.n, stream l = j % gg.n) of the gg.n = cells x per streams, as guide_launch numbers them.  STREAM LAYOUT of one evaluation:
+//   stream l,        draws 3 r .. 3 r + 2   the cell sample, stratified into cell l / per (guide_slot_sample): s3 of segment A, (s3[0], u, v) of segment B
+//   stream gg.n + j, draws 0 ..             every other number, laid out as a render slot's stream after s3: 2 skipped (the direction numbers) | 3 (d-1) walk
+//                                           numbers of A | 3 (d-2) of B | 5 (d-1) source-bounce numbers
+// Streams [0, gg.n) hold cell samples only and streams [gg.n, gg.n + gg.n * nrounds) the rest: disjoint.  tests/hostcheck/hostcheck_path_guide.cpp mirrors this.
+// mass[cell] += path_sedge_mass * gg.scale, gg.scale = 1 / (per * nrounds).  Small builds: this kernel over all slots; large ones: a filter (segment A:
+// k_secondary_edge_filter with the GuideGrid, segment B: k_path_guide_filter_b) and this kernel over the survivor list.
+template <int FL>
+__global__ __launch_bounds__(kBlock, 4) void k_path_guide_filter_b(LaunchCtx cx, GuideGrid gg, long long n, uint32_t *__restrict__ list, int *__restrict__ list_n, unsigned long long *counters) {
+    path_sedge_filter_loop<FL>(cx, n, list, list_n, counters, [&](TraversalStack &st, long long j, uint32_t &nrays) {
+        float c3[3]; int cell;
+        guide_slot_sample(gg, j, c3, cell);
+        return path_sedge_survives_b_at<FL>(cx.sc, st, c3[0], c3[1], c3[2], nrays);
+    });
+}
+
+template <int FL>
+__global__ __launch_bounds__(kBlock) void k_path_guide(LaunchCtx cx, GuideGrid gg, long long n, PathSedgeOpts po, float *__restrict__ mass, unsigned long long *counters,
+                                                       const uint32_t *__restrict__ list, const int *__restrict__ list_n) {
+    TraversalStack st; setup_lds(cx, st);
+    uint32_t nrays = 0;
+    const RngJump nojump{1ull, 0ull};
+    if (list != nullptr) n = *list_n;
+    for (long long jj = (long long) blockIdx.x * kBlock + threadIdx.x; jj < n; jj += (long long) gridDim.x * kBlock) {
+        const long long j = list != nullptr ? (long long) list[jj] : jj;
+        float c3[3]; int cell;
+        guide_slot_sample(gg, j, c3, cell);          // cell < r0 r1 r2 = the length of mass: l < gg.n = cells * per
+        Rng rest; rest.init((uint64_t) gg.n + (uint64_t) j, nojump);
+        const float a = path_sedge_mass<FL>(cx.sc, st, rest, c3, po, nrays, list == nullptr) * gg.scale;
+        if (a != 0.f) atomicAdd(mass + cell, a);
+    }
+    count_rays(counters, nrays);
+}
+
+template <int K, int FL, bool G>
 __global__ __launch_bounds__(kBlock) void k_path_sedge(LaunchCtx cx, TangentView<K, FL> tv, long long i0, long long n, float inv_sppse, float *__restrict__ dimg, long long plane,
-                                                       unsigned long long *counters, const uint32_t *__restrict__ list, const int *__restrict__ list_n, PathSedgeOpts po) {
+                                                       unsigned long long *counters, const uint32_t *__restrict__ list, const int *__restrict__ list_n, PathSedgeArgs<G> pa) {
     using R = Dual<K>;
     TraversalStack st; setup_lds(cx, st);
     uint32_t nrays = 0;
+    const PathSedgeOpts po = pa.opts();
     if (list != nullptr) n = *list_n;
     for (long long jj = (long long) blockIdx.x * kBlock + threadIdx.x; jj < n; jj += (long long) gridDim.x * kBlock) {
         const long long j = list != nullptr ? (long long) list[jj] : jj;
         Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
         const float s3[3] = {rng.next(), rng.next(), rng.next()};
-        path_secondary_edge_sample<R>(cx.sc, tv, st, rng, s3, po, nrays, list == nullptr, [&](int pixel, const Vec3<R> &value) {
+        path_secondary_edge_sample<R, G>(cx.sc, tv, st, rng, s3, po, nrays, list == nullptr, [&](int pixel, const Vec3<R> &value) {
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const float g[3] = {value.x.d[k] * inv_sppse, value.y.d[k] * inv_sppse, value.z.d[k] * inv_sppse};
@@ -83,18 +137,19 @@ __global__ __launch_bounds__(kBlock) void k_path_sedge(LaunchCtx cx, TangentView
     count_rays(counters, nrays);
 }
 
-template <int FL>
+template <int FL, bool G>
 __global__ __launch_bounds__(kBlock) void k_path_sedge_rev(LaunchCtx cx, DeviceSink<FL> sink, long long i0, long long n, float inv_sppse, const float *__restrict__ adj_img,
-                                                           unsigned long long *counters, const uint32_t *__restrict__ list, const int *__restrict__ list_n, PathSedgeOpts po) {
+                                                           unsigned long long *counters, const uint32_t *__restrict__ list, const int *__restrict__ list_n, PathSedgeArgs<G> pa) {
     TraversalStack st; setup_lds(cx, st);
     sink.begin(dyn_lds_floats(cx.off_sink));
     uint32_t nrays = 0;
+    const PathSedgeOpts po = pa.opts();
     if (list != nullptr) n = *list_n;
     for (long long jj = (long long) blockIdx.x * kBlock + threadIdx.x; jj < n; jj += (long long) gridDim.x * kBlock) {
         const long long j = list != nullptr ? (long long) list[jj] : jj;
         Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
         const float s3[3] = {rng.next(), rng.next(), rng.next()};
-        path_secondary_edge_reverse(sink, cx.sc, st, rng, s3, po, inv_sppse, adj_img, nrays, list == nullptr);
+        path_secondary_edge_reverse<G>(sink, cx.sc, st, rng, s3, po, inv_sppse, adj_img, nrays, list == nullptr);
     }
     sink.end();
     count_rays(counters, nrays);
@@ -109,41 +164,50 @@ inline bool path_sedge_split(const psdr_scene_s *h, long long n) {          // t
     const int split_env = h->opt.sedge_split;
     return !(split_env == 0 || (split_env < 0 && n < (1ll << 18))) && n <= 0x7fffffffLL;
 }
+inline PathGuide path_guide_of(const psdr_scene_s *h) {
+    PathGuide g;
+    g.cmf = h->pg_cmf; g.pmf = h->pg_pmf; g.sum = h->pg_sum;
+    g.r0 = h->pg_reso[0]; g.r1 = h->pg_reso[1]; g.r2 = h->pg_reso[2]; g.n = g.r0 * g.r1 * g.r2;
+    return g;
+}
 // filter pass of segment B: the survivor list shares the handle's block with segment A's (the passes of one call follow each other on the stream)
 template <int FL>
-int path_sedge_filter_b(psdr_scene_s *h, const LaunchCtx &cx, long long i0, long long n, const uint32_t **list, const int **list_n, hipStream_t s) {
+int path_sedge_filter_b(psdr_scene_s *h, const LaunchCtx &cx, long long i0, long long n, const uint32_t **list, const int **list_n, hipStream_t s, const PathGuide &gb, const GuideGrid *gg = nullptr) {
     const size_t need = 256 + (size_t) n * sizeof(uint32_t);
     if (int rc = scratch_reserve(&h->d_se_list, &h->se_list_bytes, need, s, "secondary-edge survivor list")) return rc;
     int *cnt = reinterpret_cast<int *>(h->d_se_list);
     uint32_t *lst = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(h->d_se_list) + 256);
     HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_path_sedge_filter<FL>, dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, i0, n, lst, cnt, h->d_counters);
+    if (gg != nullptr) hipLaunchKernelGGL(k_path_guide_filter_b<FL>, dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, *gg, n, lst, cnt, h->d_counters);
+    else if (gb.cmf != nullptr) hipLaunchKernelGGL(k_path_sedge_filter_g<FL>, dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, i0, n, lst, cnt, h->d_counters, gb);
+    else hipLaunchKernelGGL(k_path_sedge_filter<FL>, dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, i0, n, lst, cnt, h->d_counters);
     HIP_TRY(hipGetLastError());
     *list = lst; *list_n = cnt;
     return 0;
 }
-// launch(list, list_n, grid slots, po) starts the evaluating kernel (forward or reverse); cxf: the context the filters stage the scene with
+// launch(list, list_n, grid slots, po, guided) starts the evaluating kernel (forward or reverse; guided: its G = true instance); cxf: the context the filters stage the scene with
 template <int FL, class Launch>
 int path_sedge_passes(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCtx &cxf, long long i0, long long n, hipStream_t s, Launch &&launch) {
-    if (h->desc.guide_cmf != nullptr && h->desc.num_guide_cells > 0) return fail("PSDR_FLAG_PATH_SEDGES: a guiding grid is not supported for PathTracer slots");
     PathSedgeOpts po{o->max_depth, h->opt.pt_sedge & 3, h->opt.pt_sedge_walk};
     if (po.max_depth < 2) po.seg &= 1;
+    if ((po.seg & 2) && h->pg_cmf != nullptr) po.gb = path_guide_of(h);          // (a segment that is switched off ignores its grid)
+    const bool ga = (po.seg & 1) && h->desc.guide_cmf != nullptr && h->desc.num_guide_cells > 0, gb = po.gb.cmf != nullptr;
     if (!path_sedge_split(h, n)) {
-        if (po.seg != 0) { launch(nullptr, nullptr, n, po); HIP_TRY(hipGetLastError()); }
+        if (po.seg != 0) { launch(nullptr, nullptr, n, po, ga || gb); HIP_TRY(hipGetLastError()); }
         return 0;
     }
     if (po.seg & 1) {
         const uint32_t *list = nullptr; const int *list_n = nullptr;
         if (int rc = secondary_edge_filter<FL>(h, cxf, i0, n, &list, &list_n, s)) return rc;
         PathSedgeOpts pa = po; pa.seg = 1;
-        launch(list, list_n, list ? std::max(n / 16, 1ll << 16) : n, pa);
+        launch(list, list_n, list ? std::max(n / 16, 1ll << 16) : n, pa, ga);
         HIP_TRY(hipGetLastError());
     }
     if (po.seg & 2) {
         const uint32_t *list = nullptr; const int *list_n = nullptr;
-        if (int rc = path_sedge_filter_b<FL>(h, cxf, i0, n, &list, &list_n, s)) return rc;
+        if (int rc = path_sedge_filter_b<FL>(h, cxf, i0, n, &list, &list_n, s, po.gb)) return rc;
         PathSedgeOpts pb = po; pb.seg = 2;
-        launch(list, list_n, std::max(n / 4, 1ll << 16), pb);
+        launch(list, list_n, std::max(n / 4, 1ll << 16), pb, gb);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -158,9 +222,13 @@ int path_sedge_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tang
     if (int rc = make_ctx(h, o, 2, cx)) return rc;
     const long long i0 = WH * o->sppse_begin, n = WH * (o->sppse_end - o->sppse_begin);
     h->slots[2] += (uint64_t) n;
-    return path_sedge_passes<FL>(h, o, cx, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppse,
-                           dimg, WH * 3, h->d_counters, list, list_n, po);
+    return path_sedge_passes<FL>(h, o, cx, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po, bool guided) {
+        if (guided)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL, true>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppse,
+                               dimg, WH * 3, h->d_counters, list, list_n, PathSedgeArgs<true>{po.max_depth, po.seg, po.walk, po.gb});
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL, false>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppse,
+                               dimg, WH * 3, h->d_counters, list, list_n, PathSedgeArgs<false>{po.max_depth, po.seg, po.walk});
     });
 }
 // forward mode: adds the term to the K derivative images psdr_render_d_fwd has rendered (same stream)
@@ -188,21 +256,52 @@ int path_sedge_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_
     cx.off_sink = lds_bytes(cx, h);
     const int dyn_bytes = cx.off_sink + cache_bytes;
     if (dyn_bytes > h->lds_limit) return fail("psdr_render_d_rev: the secondary-edge launch needs " + std::to_string(dyn_bytes) + " bytes of LDS per workgroup");
-    if (dyn_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_path_sedge_rev<FL>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes));
+    if (dyn_bytes > 48 * 1024) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_path_sedge_rev<FL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_path_sedge_rev<FL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes));
+    }
     LaunchCtx cxf;                                              // the filters stage the scene like a forward kernel (no gradient cache in LDS)
     if (int rc = make_ctx(h, o, 2, cxf)) return rc;
-    return path_sedge_passes<FL>(h, o, cxf, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po) {
-        hipLaunchKernelGGL(k_path_sedge_rev<FL>, dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, cx, sink, i0, n, 1.f / (float) o->sppse, adj_img,
-                           h->d_counters, list, list_n, po);
+    return path_sedge_passes<FL>(h, o, cxf, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po, bool guided) {
+        if (guided)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge_rev<FL, true>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, cx, sink, i0, n, 1.f / (float) o->sppse, adj_img,
+                               h->d_counters, list, list_n, PathSedgeArgs<true>{po.max_depth, po.seg, po.walk, po.gb});
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge_rev<FL, false>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, cx, sink, i0, n, 1.f / (float) o->sppse, adj_img,
+                               h->d_counters, list, list_n, PathSedgeArgs<false>{po.max_depth, po.seg, po.walk});
     });
+}
+
+// the guiding-grid build of one segment (the C ABI has checked the arguments and zeroed out_mass); evaluated unguided
+template <int FL>
+int path_guide_build(psdr_scene_s *h, const psdr_render_opts *o, int segment, const int32_t reso[4], int nrounds, float *out_mass, hipStream_t s) {
+    LaunchCtx cx;
+    if (int rc = make_ctx(h, o, 2, cx)) return rc;
+    cx.sc.d.guide_cmf = nullptr; cx.sc.d.num_guide_cells = 0;
+    const long long n = (long long) reso[0] * reso[1] * reso[2] * reso[3], total = n * nrounds;
+    const GuideGrid gg{reso[0], reso[1], reso[2], reso[3], (int) n, 1.f / ((float) reso[3] * (float) nrounds)};
+    const PathSedgeOpts po{o->max_depth, segment, h->opt.pt_sedge_walk};
+    const uint32_t *list = nullptr; const int *list_n = nullptr;
+    long long grid_slots = total;
+    if (path_sedge_split(h, total)) {
+        if (segment == 1) {
+            if (int rc = secondary_edge_filter<FL>(h, cx, 0, total, &list, &list_n, s, &gg)) return rc;
+            grid_slots = std::max(total / 16, 1ll << 16);
+        } else {
+            if (int rc = path_sedge_filter_b<FL>(h, cx, 0, total, &list, &list_n, s, PathGuide{}, &gg)) return rc;
+            grid_slots = std::max(total / 4, 1ll << 16);
+        }
+    }
+    hipLaunchKernelGGL(k_path_guide<FL>, dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, gg, total, po, out_mass, h->d_counters, list, list_n);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 }  // namespace
 
 namespace psdr_host {
 const PathSedgeOps *PSDR_CAT(path_sedge_ops_, PSDR_VARIANT_FLAGS)() {
     constexpr int FL = PSDR_VARIANT_FLAGS;
-    static const PathSedgeOps ops{&path_sedge_fwd<FL>, &path_sedge_rev<FL>};
+    static const PathSedgeOps ops{&path_sedge_fwd<FL>, &path_sedge_rev<FL>, &path_guide_build<FL>};
     return &ops;
 }
 }  // namespace psdr_host

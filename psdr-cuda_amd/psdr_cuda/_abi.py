@@ -85,7 +85,7 @@ TANGENT_FIELDS = ("tri_info", "texels", "emitter_rad", "cam_to_world", "sec_edge
 HIP_SYMBOLS = (
     "psdr_last_error", "psdr_version", "psdr_abi_struct_sizes", "psdr_scene_create", "psdr_scene_destroy", "psdr_scene_set_option", "psdr_scene_set_tables",
     "psdr_bvh_build", "psdr_bvh_stats", "psdr_scene_info", "psdr_trace", "psdr_render_c", "psdr_render_d_fwd", "psdr_render_d_rev",
-    "psdr_guide_build", "psdr_get_counters", "psdr_scene_rev_layout", "psdr_scene_seed_info", "psdr_scene_logd_info",
+    "psdr_guide_build", "psdr_scene_set_path_guide", "psdr_path_guide_build", "psdr_get_counters", "psdr_scene_rev_layout", "psdr_scene_seed_info", "psdr_scene_logd_info",
     "psdr_geo_world_vertices_fwd", "psdr_geo_world_vertices_rev", "psdr_geo_tri_rows_fwd", "psdr_geo_tri_rows_rev", "psdr_geo_sec_edges_fwd", "psdr_geo_sec_edges_rev", "psdr_geo_prim_edges_fwd", "psdr_geo_prim_edges_rev",
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
     "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
@@ -129,6 +129,8 @@ def load_hip():
     lib.psdr_render_d_fwd.argtypes = [vp, C.POINTER(RenderOpts), i32, C.POINTER(Tangents), vp, vp, vp]
     lib.psdr_render_d_rev.argtypes = [vp, C.POINTER(RenderOpts), vp, vp, C.POINTER(Grads), vp]
     lib.psdr_guide_build.argtypes = [vp, C.POINTER(RenderOpts), C.POINTER(i32), i32, vp, vp]
+    lib.psdr_scene_set_path_guide.argtypes = [vp, C.POINTER(i32), vp, vp, C.c_float]
+    lib.psdr_path_guide_build.argtypes = [vp, C.POINTER(RenderOpts), i32, C.POINTER(i32), i32, vp, vp]
     lib.psdr_get_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.psdr_scene_info.argtypes = [vp, C.POINTER(i32)]
     lib.psdr_scene_rev_layout.argtypes = [vp, C.POINTER(i32)]

@@ -424,8 +424,10 @@ class PathTracer(Integrator):
     secondary_edges=True: renderD also evaluates the secondary-edge boundary term (moving shadow and occlusion boundaries under global illumination,
     SURVEY App. F, F3) on scene.opts.sppse slots per pixel, in forward and reverse mode; max_depth <= 8.  Without it the geometry gradient of renderD
     holds the interior and the primary-edge term only and is wrong wherever a shadow edge moves.  The default is False because turning the term on
-    changes the results of existing callers; a later change may flip it.  preprocess_secondary_edges stays a DirectIntegrator feature (these slots are
-    not guided)."""
+    changes the results of existing callers; a later change may flip it.
+
+    The slots of the term are importance-sampled by up to two guiding grids per sensor, one per boundary segment of a slot, built by
+    preprocess_path_secondary_edges (preprocess_secondary_edges stays DirectIntegrator's call: it builds one grid)."""
     _type_name = "PathTracer"
     _kind = _abi.INTEGRATOR_PATH
 
@@ -436,3 +438,59 @@ class PathTracer(Integrator):
         self.secondary_edges = bool(secondary_edges)
         self.bsdf_samples = self.light_samples = 1
         self.hide_emitters = False
+
+    def _prepare(self, scene, tb, guide):
+        """guide: None or (grid of segment A or None, grid of segment B or None).  Segment A's grid travels in the descriptor like DirectIntegrator's;
+        segment B's lives on the handle, where psdr_scene_set_tables drops it: it is set again after every set_tables."""
+        ga, gb = guide if guide is not None else (None, None)
+        lib, keep = super()._prepare(scene, tb, ga)
+        if gb is not None:
+            reso, cmf, pmf, total = gb
+            cmf, pmf = (t.detach().to(device="cuda", dtype=torch.float32).contiguous() for t in (cmf, pmf))
+            keep += [cmf, pmf]
+            _abi.check(lib, lib.psdr_scene_set_path_guide(scene._native, (C.c_int32 * 3)(*[int(r) for r in reso]), cmf.data_ptr(), pmf.data_ptr(), float(total)))
+        return lib, keep
+
+    def preprocess_path_secondary_edges(self, scene, sensor_id, resolution, resolution_indirect=None, nrounds=1):
+        """Builds the guiding grids of the secondary-edge term for one sensor: `resolution` for the direct-source segment of a slot (over the slot's three
+        numbers, as DirectIntegrator's grid), `resolution_indirect` for the indirect-source segment (over the edge number and the two direction numbers).
+        Both are 4-vectors (cells along the three numbers, sample streams per cell) as in DirectIntegrator.preprocess_secondary_edges; None leaves that
+        segment unguided.  Returns (HyperCubeDistribution3f or None, HyperCubeDistribution3f or None).  Every later renderD of the sensor uses the grids,
+        in forward and reverse mode; calling the method again replaces them."""
+        if not self.secondary_edges:
+            raise RuntimeError("preprocess_path_secondary_edges: PathTracer(secondary_edges=False) never evaluates the slots the grids would guide")
+        if self.max_depth > _abi.MAX_PATH_SEDGE_DEPTH:
+            raise RuntimeError("preprocess_path_secondary_edges: max_depth > %d is not supported for the secondary-edge term" % _abi.MAX_PATH_SEDGE_DEPTH)
+        psdr_assert(nrounds > 0)
+        psdr_assert(scene.is_ready(), "Scene needs to be configured!")
+        psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")
+        tb = scene.tables(sensor_id, capacity=True)
+        lib, keep = self._prepare(scene, tb, None)
+        opts = self._opts(scene, with_edges=True)
+        dist = _dist()
+        out, grids = [], []
+        for segment, resolution_s in ((1, resolution), (2, resolution_indirect)):
+            if resolution_s is None:
+                out.append(None)
+                grids.append(None)
+                continue
+            reso = [int(r) for r in np.asarray(resolution_s).reshape(-1)]
+            psdr_assert(len(reso) == 4)
+            cells = reso[0] * reso[1] * reso[2]
+            psdr_assert(cells * reso[3] < 2 ** 31 - 1)
+            mass = torch.zeros(cells, dtype=torch.float32, device="cuda")
+            _abi.check(lib, lib.psdr_path_guide_build(scene._native, C.byref(opts), segment, (C.c_int32 * 4)(*reso), int(nrounds), mass.data_ptr(), _stream_ptr()))
+            if dist:
+                dist.all_reduce(mass)          # every rank evaluated all cells; keep replicas bit-identical
+                mass /= dist.get_world_size()
+            w = HyperCubeDistribution3f()
+            w.set_resolution(reso[:3])
+            w.set_mass(mass)
+            out.append(w)
+            grids.append((reso[:3], w.m_distrb.m_cmf, w.m_distrb.m_pmf, w.m_distrb.m_sum))
+        torch.cuda.synchronize()
+        if grids[0] is None and grids[1] is None:
+            self._guide.pop(sensor_id, None)
+        else:
+            self._guide[sensor_id] = tuple(grids)
+        return tuple(out)
