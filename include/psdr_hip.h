@@ -86,6 +86,12 @@ extern "C" {
 #define PSDR_INTEGRATOR_DIRECT 0
 #define PSDR_INTEGRATOR_PATH   1
 #define PSDR_INTEGRATOR_FIELD  2
+/* CollocatedIntegrator (build-defined, csrc/psdr_collocated.h): a point light of unit intensity at the camera position.  For a camera ray with origin o
+   that hits `its`:  Li = f(its; wi = its.wi, wo = its.wi) / |its.p - o|^2  (0 on a miss), f = the BSDF value with its cosine, in the shading frame of the
+   hit.  Emitters add nothing (no Le, no emitter sampling; a scene without any emitter is valid); no draws beyond the film jitter: two per camera slot,
+   one per primary-edge slot.  Gradients: interior + primary edges -- a point seen from the camera is seen from the light, so there is no secondary-edge
+   term and sppse is ignored.  The caller scales image, derivative images and adjoint image by the light's RGB intensity. */
+#define PSDR_INTEGRATOR_COLLOCATED 3
 /* FieldExtractionIntegrator fields (src/integrator/field.cpp:10-54) */
 #define PSDR_FIELD_SILHOUETTE 0
 #define PSDR_FIELD_POSITION   1

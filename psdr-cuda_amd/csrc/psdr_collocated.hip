@@ -1,0 +1,320 @@
+// psdr_collocated.hip -- the kernels of the CollocatedIntegrator (PSDR_INTEGRATOR_COLLOCATED, psdr_collocated.h) for the scene flag set PSDR_VARIANT_FLAGS,
+// and their launches.  A translation unit of its own, compiled once per flag set like psdr_path_sedge.hip and for the same reason: new
+// kernels inside psdr_kernels.h change the code of the existing ones.  The C ABI picks collocated_ops_<flags>() for this integrator BEFORE the variant's own
+// dispatch (psdr_hip.hip), so integrator kinds 0-2 never come here and this kind never reaches psdr_variant.hip.
+// Shared with the other kernels: primary_ray, closest_hit / intersect (every scene form), the film-sample and splat machinery of k_camera (wave_segmented_sum,
+// the plain-store path of a wave that owns its pixels), Bsdf / BsdfRev, DeviceSink, PrimaryEdgeSink and the pixel-sorted slot order of the primary-edge launches.
+#ifndef PSDR_WIDE_TREE
+#if PSDR_VARIANT_FLAGS == 6
+#define PSDR_WIDE_TREE 1
+#else
+#define PSDR_WIDE_TREE 0
+#endif
+#endif
+#ifndef PSDR_LEAF_PAIR
+#if PSDR_VARIANT_FLAGS == 6
+#define PSDR_LEAF_PAIR 1
+#else
+#define PSDR_LEAF_PAIR 0
+#endif
+#endif
+#include "psdr_kernels.h"
+#include "psdr_collocated.h"
+
+#ifndef PSDR_VARIANT_FLAGS
+#error "compile with -DPSDR_VARIANT_FLAGS=0|1|2|3|4|6|8|10"
+#endif
+#define PSDR_CAT2(a, b) a##b
+#define PSDR_CAT(a, b) PSDR_CAT2(a, b)
+
+namespace {
+
+// Resident waves per SIMD (workgroups of kBlock = 256 lanes per CU), chosen from the compiler's resource report of THESE kernels
+// (profiles/collocated_resources.txt: -Rpass-analysis=kernel-resource-usage), not from the Direct kernels' constants: no path state, no shadow ray.
+// No instance spills a VGPR at its bound.
+// `rough`: the flag sets that carry the rough-conductor code (GGX + conductor Fresnel with wi = wo); the others evaluate a Lambertian only.
+template <class G, class R, int FL> constexpr int colloc_camera_waves() {
+    constexpr bool rough = (FL & kSceneRough) != 0;
+    if (!is_ad<R>()) return rough ? 7 : 8;                                 // renderC
+    constexpr int K = ad_traits<R>::K;
+    if (!is_ad<G>()) return K == 1 ? (rough ? 5 : 8) : (rough ? 3 : 4);   // material duals
+    return K == 1 ? (rough ? 4 : 5) : (rough ? 2 : 3);                    // geometry duals
+}
+template <int FL, bool GEO> constexpr int colloc_rev_waves() {
+    constexpr bool rough = (FL & kSceneRough) != 0;
+    return GEO ? (rough ? 2 : 3) : (rough ? 4 : 8);
+}
+// K = 0: the reverse kernel.  The Lambertian K = 1 and reverse instances fit seven waves (72 VGPRs) only without a tree walk: with one they spill 8-20 VGPRs there
+// and run at five -- the one place where not spilling costs waves.
+template <int K, int FL> constexpr int colloc_edge_waves() { return ((FL & kSceneRough) != 0 || K == 3) ? 4 : ((FL & kSceneTiny) != 0 ? 7 : 5); }
+
+// ---------------------------------------------------------------------- camera kernel (k_camera's slot order, film sums and splat)
+template <class G, class R, int FL>
+__global__ __launch_bounds__(kBlock, (colloc_camera_waves<G, R, FL>())) void k_colloc_camera(LaunchCtx cx, TV<R, FL> tv, int spp, int s_begin, SlotDiv nsp, long long n, float inv_spp,
+                                                                                          float *__restrict__ img, float *__restrict__ dimg, long long plane,
+                                                                                          unsigned long long *counters, int own) {
+    constexpr int K = ad_traits<R>::K;
+    constexpr int NV = 3 * (1 + K);
+    TraversalStack st; setup_lds(cx, st, tv);
+    uint32_t nrays = 0;
+    const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
+    for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
+        const bool in = j < n;
+        int pixel = 0x7fffffff, s_in = 0;
+        if (in) slot_to_pixel(j, nsp, pixel, s_in);
+        float v[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) v[i] = 0.f;
+        if (in) {
+            const uint64_t slot = (uint64_t) pixel * (uint64_t) spp + (uint64_t) (s_begin + s_in);
+            const Vec3<R> r = collocated_camera_sample<G, R>(cx.sc, tv, st, cx.jump, pixel, slot, nrays);
+            v[0] = val(r.x) * inv_spp; v[1] = val(r.y) * inv_spp; v[2] = val(r.z) * inv_spp;
+#pragma unroll
+            for (int k = 0; k < K; ++k) { v[3 + 3 * k] = tangent(r.x, k) * inv_spp; v[4 + 3 * k] = tangent(r.y, k) * inv_spp; v[5 + 3 * k] = tangent(r.z, k) * inv_spp; }
+        }
+        const bool head = wave_segmented_sum<NV>(pixel, v);
+        if (head && in) {
+            float *p = img + (size_t) pixel * 3;
+            if (own) {
+                // every sample of the pixel sits in this wave (run_camera's rule): plain stores
+                p[0] = v[0]; p[1] = v[1]; p[2] = v[2];
+#pragma unroll
+                for (int k = 0; k < K; ++k) { float *q = dimg + (size_t) k * plane + (size_t) pixel * 3; q[0] = v[3 + 3 * k]; q[1] = v[4 + 3 * k]; q[2] = v[5 + 3 * k]; }
+            } else {
+                if (v[0] != 0.f) atomicAdd(p, v[0]);
+                if (v[1] != 0.f) atomicAdd(p + 1, v[1]);
+                if (v[2] != 0.f) atomicAdd(p + 2, v[2]);
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    float *q = dimg + (size_t) k * plane + (size_t) pixel * 3;
+                    if (v[3 + 3 * k] != 0.f) atomicAdd(q, v[3 + 3 * k]);
+                    if (v[4 + 3 * k] != 0.f) atomicAdd(q + 1, v[4 + 3 * k]);
+                    if (v[5 + 3 * k] != 0.f) atomicAdd(q + 2, v[5 + 3 * k]);
+                }
+            }
+        }
+    }
+    count_rays(counters, nrays);
+}
+
+// ---------------------------------------------------------------------- reverse camera kernel (k_camera_rev without a path record)
+template <int FL, bool GEO>
+__global__ __launch_bounds__(kBlock, (colloc_rev_waves<FL, GEO>())) void k_colloc_camera_rev(LaunchCtx cx, DeviceSink<FL> sink, int spp, int s_begin, SlotDiv nsp, long long n, float inv_spp,
+                                                                                          const float *__restrict__ adj_img, float *__restrict__ img, unsigned long long *counters) {
+    TraversalStack st; setup_lds(cx, st);
+    sink.begin(dyn_lds_floats(cx.off_sink));
+    uint32_t nrays = 0;
+    const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
+    for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
+        const bool in = j < n;
+        int pixel = 0x7fffffff, s_in = 0;
+        if (in) slot_to_pixel(j, nsp, pixel, s_in);
+        float v[3] = {0.f, 0.f, 0.f};
+        PrimaryGrad pg; pg.clear();
+        if (in) {
+            const uint64_t slot = (uint64_t) pixel * (uint64_t) spp + (uint64_t) (s_begin + s_in);
+            const float *a = adj_img + (size_t) pixel * 3;
+            const Vec3f r = collocated_sample_reverse<GEO>(sink, pg, cx.sc, st, cx.jump, pixel, slot, Vec3f{a[0] * inv_spp, a[1] * inv_spp, a[2] * inv_spp}, nrays);
+            v[0] = r.x * inv_spp; v[1] = r.y * inv_spp; v[2] = r.z * inv_spp;
+        }
+        // primary-triangle row: one add per run of lanes that hit the same triangle
+        if (GEO && sink.g.g_tri_info != nullptr) {
+            const bool head = wave_run_sum<kPrimaryWords, (FL & kSceneRough) == 0 || PSDR_DPP_ALWAYS>(pg.tri, pg.w);
+            if (head && pg.tri >= 0) {
+#pragma unroll
+                for (int w = 0; w < kPrimaryWords; ++w) sink.add_tri(pg.tri, w, pg.w[w]);
+            }
+        }
+        if (img != nullptr) {
+            const bool head = wave_segmented_sum<3>(pixel, v);
+            if (head && in) {
+                float *p = img + (size_t) pixel * 3;
+                if (v[0] != 0.f) atomicAdd(p, v[0]);
+                if (v[1] != 0.f) atomicAdd(p + 1, v[1]);
+                if (v[2] != 0.f) atomicAdd(p + 2, v[2]);
+            }
+        }
+    }
+    sink.end();
+    count_rays(counters, nrays);
+}
+
+// ---------------------------------------------------------------------- primary-edge kernels (k_primary_edge / k_primary_edge_rev with this estimator)
+template <int K, int FL>
+__global__ __launch_bounds__(kBlock, (colloc_edge_waves<K, FL>())) void k_colloc_edge(LaunchCtx cx, TangentView<K, FL> tv, long long i0, long long n, float inv_sppe, float *__restrict__ dimg,
+                                                                                long long plane, unsigned long long *counters, const uint32_t *__restrict__ order) {
+    TraversalStack st; setup_lds(cx, st);
+    uint32_t nrays = 0;
+    const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
+    for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
+        float tan[K][3];
+        int pixel = -1;
+        if (j < n) {
+            const long long jj = order ? (long long) order[j] : j;          // pixel-sorted evaluation order (psdr_hip.hip)
+            pixel = collocated_edge_sample<K, FL>(cx.sc, tv, st, cx.jump, (uint64_t) (i0 + jj), inv_sppe, tan, nrays);
+        }
+        float v[3 * K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[3 * k + c] = pixel >= 0 ? tan[k][c] : 0.f;
+        const bool head = wave_run_sum<3 * K>(pixel, v);          // one atomic per run of equal pixels
+        if (head && pixel >= 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    if (v[3 * k + c] != 0.f) atomicAdd(dimg + (size_t) k * plane + (size_t) pixel * 3 + c, v[3 * k + c]);
+        }
+    }
+    count_rays(counters, nrays);
+}
+template <int FL>
+__global__ __launch_bounds__(kBlock, (colloc_edge_waves<0, FL>())) void k_colloc_edge_rev(LaunchCtx cx, PrimaryEdgeSink<FL> sink, long long i0, long long n, float inv_sppe,
+                                                                                    const float *__restrict__ adj_img, unsigned long long *counters, const uint32_t *__restrict__ order) {
+    TraversalStack st; setup_lds(cx, st);
+    uint32_t nrays = 0;
+    const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
+    for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
+        float w[4] = {0.f, 0.f, 0.f, 0.f};
+        int edge = -1;
+        if (j < n) edge = collocated_edge_reverse_values<FL>(cx.sc, st, cx.jump, (uint64_t) (i0 + (order ? (long long) order[j] : j)), inv_sppe, adj_img, nrays, w);
+        const bool head = wave_run_sum<4>(edge, w);               // one atomic per run of equal edges
+        if (head && edge >= 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sink.add_pedge(edge, i, w[i]);
+        }
+    }
+    count_rays(counters, nrays);
+}
+
+// ============================================================================ launches
+template <class G, class R, int FL>
+int colloc_run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, float *img, float *dimg, hipStream_t s) {
+    const long long WH = (long long) h->desc.width * h->desc.height;
+    const int nsp = o->spp_end - o->spp_begin;
+    if (o->spp <= 0 || nsp <= 0) return 0;
+    LaunchCtx cx;
+    if (int rc = make_ctx(h, o, 0, cx)) return rc;
+    const long long n = WH * nsp;
+    h->slots[0] += (uint64_t) n;
+    const int own = (h->opt.own_pixels != 0 && nsp <= 64 && 64 % nsp == 0) ? 1 : 0;          // run_camera's rule
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colloc_camera<G, R, FL>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, o->spp, o->spp_begin,
+                       SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <int FL>
+int colloc_render_c(psdr_scene_s *h, const psdr_render_opts *o, float *out_img, hipStream_t s) {
+    const TangentView<0, FL> tv0{};
+    return colloc_run_camera<float, float, FL>(h, o, tv0, out_img, nullptr, s);
+}
+
+template <int K, int FL>
+int colloc_render_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s) {
+    const long long WH = (long long) h->desc.width * h->desc.height;
+    TangentView<K, FL> tv;
+    for (int k = 0; k < K; ++k) tv.t[k] = tangents[k];
+    HIP_TRY(hipMemsetAsync(img, 0, sizeof(float) * WH * 3, s));
+    HIP_TRY(hipMemsetAsync(dimg, 0, sizeof(float) * WH * 3 * K, s));
+    // geometry stays in plain fp32 when only material tables carry tangents
+    bool geo = false;
+    for (int k = 0; k < K; ++k) geo = geo || tangents[k].d_tri_info || tangents[k].d_cam_to_world;
+    if (geo) { if (int rc = colloc_run_camera<Dual<K>, Dual<K>, FL>(h, o, tv, img, dimg, s)) return rc; }
+    else { if (int rc = colloc_run_camera<float, Dual<K>, FL>(h, o, tv, img, dimg, s)) return rc; }
+    if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0) {
+        LaunchCtx cx;
+        if (int rc = make_ctx(h, o, 1, cx)) return rc;
+        const long long i0 = WH * o->sppe_begin, n = WH * (o->sppe_end - o->sppe_begin);
+        h->slots[1] += (uint64_t) n;
+        const uint32_t *order = nullptr;
+        if (int rc = primary_edge_order(h, cx, i0, n, &order, s)) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colloc_edge<K, FL>), dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppe, dimg, WH * 3,
+                           h->d_counters, order);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;          // (sppse: this integrator has no secondary-edge term)
+}
+template <int FL>
+int colloc_render_fwd(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s) {
+    switch (K) {
+        case 1: return colloc_render_fwd_k<1, FL>(h, o, tangents, img, dimg, s);
+        case 3: return colloc_render_fwd_k<3, FL>(h, o, tangents, img, dimg, s);
+        default: return fail("psdr_render_d_fwd: K must be 1 or 3");
+    }
+}
+
+template <int FL>
+int colloc_render_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, hipStream_t s) {
+    const long long WH = (long long) h->desc.width * h->desc.height;
+    if (out_img) HIP_TRY(hipMemsetAsync(out_img, 0, sizeof(float) * WH * 3, s));
+    DeviceSink<FL> sink{}; sink.g = *grads; sink.L = make_sink_layout(h, grads);
+    if ((FL & kSceneTiny) != 0 && PSDR_TINY_DIRECT_ROWS && grads->g_tri_info != nullptr && !(h->hot_identity && sink.L.hot_rows == h->desc.num_tris))
+        return fail("psdr_render_d_rev: the gradient cache of a scene without a tree does not hold every triangle row");
+    sink.L.priv_rows = 0; sink.L.priv_emitter = -1; sink.L.priv_regs = 0;          // no light samples: no private emitter rows; one vertex per slot: nothing deferred
+    sink.L.pend_rows = 0; sink.L.pend_off = 0;
+    const int nsp = o->spp_end - o->spp_begin;
+    if (o->spp > 0 && nsp > 0) {
+        LaunchCtx cx;
+        if (int rc = make_ctx(h, o, 0, cx)) return rc;
+        const long long n = WH * nsp;
+        h->slots[0] += (uint64_t) n;
+        const bool geo = grads->g_tri_info != nullptr || grads->g_cam_to_world != nullptr;
+        const int cache_bytes = sink_bytes(sink.L);
+        plan_lds(h, cx, cache_bytes);
+        cx.off_sink = lds_bytes(cx, h);
+        const int dyn_bytes = cx.off_sink + cache_bytes;
+        if (dyn_bytes > h->lds_limit) return fail("psdr_render_d_rev: the launch needs " + std::to_string(dyn_bytes) + " bytes of LDS per workgroup (traversal stacks + gradient cache), the device offers " +
+                                                  std::to_string(h->lds_limit));
+        {
+            int32_t *r = h->rev_layout;                                 // psdr_scene_rev_layout
+            r[0] = sink.L.tex_n; r[1] = sink.L.rad_n; r[2] = sink.L.env_n; r[3] = sink.L.hot_rows; r[4] = sink.L.rep; r[8] = 0;
+            r[10] = h->hot_identity ? 1 : 0; r[14] = h->hot_rows;
+        }
+#define PSDR_LAUNCH_COLLOC_REV(GEO)                                                                                                                                      \
+        do { if (dyn_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_colloc_camera_rev<FL, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes)); \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colloc_camera_rev<FL, GEO>), dim3(launch_blocks(h, n)), dim3(kBlock), dyn_bytes, s, cx, sink, o->spp, o->spp_begin, SlotDiv(nsp), n,                \
+                           1.f / (float) o->spp, adj_img, out_img, h->d_counters); } while (0)
+        if (geo) PSDR_LAUNCH_COLLOC_REV(true); else PSDR_LAUNCH_COLLOC_REV(false);
+#undef PSDR_LAUNCH_COLLOC_REV
+        HIP_TRY(hipGetLastError());
+    }
+    if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0 && grads->g_prim_edge) {
+        LaunchCtx cx;
+        if (int rc = make_ctx(h, o, 1, cx)) return rc;
+        const long long i0 = WH * o->sppe_begin, n = WH * (o->sppe_end - o->sppe_begin);
+        h->slots[1] += (uint64_t) n;
+        // replicated gradient table (PrimaryEdgeSink), as render_rev
+        const long long pe_words = (long long) h->desc.num_prim_edges * PSDR_PEDGE_STRIDE;
+        int reps = 1;
+        while (reps < 64 && (long long) (reps * 2) * pe_words * 4 <= (64ll << 20)) reps *= 2;
+        if (n < (1ll << 18)) reps = 1;
+        if (reps > 1) {
+            const size_t need = (size_t) reps * pe_words * sizeof(float);
+            if (int rc = scratch_reserve(&h->d_pe_rep, &h->pe_rep_bytes, need, s, "primary-edge gradient replicas")) return rc;
+            HIP_TRY(hipMemsetAsync(h->d_pe_rep, 0, need, s));
+        }
+        const PrimaryEdgeSink<FL> pe_sink{reps > 1 ? reinterpret_cast<float *>(h->d_pe_rep) : grads->g_prim_edge, pe_words, reps};
+        const uint32_t *order = nullptr;
+        if (int rc = primary_edge_order(h, cx, i0, n, &order, s)) return rc;
+        h->rev_layout[9] = reps; h->rev_layout[15] = order != nullptr ? 1 : 0;
+        hipLaunchKernelGGL(k_colloc_edge_rev<FL>, dim3(launch_blocks(h, n, big_launch_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, pe_sink, i0, n, 1.f / (float) o->sppe, adj_img,
+                           h->d_counters, order);
+        HIP_TRY(hipGetLastError());
+        if (reps > 1) {
+            hipLaunchKernelGGL(k_sum_replicas, dim3((unsigned) ((pe_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, grads->g_prim_edge, reinterpret_cast<const float *>(h->d_pe_rep), pe_words, reps);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+namespace psdr_host {
+const CollocatedOps *PSDR_CAT(collocated_ops_, PSDR_VARIANT_FLAGS)() {
+    constexpr int FL = PSDR_VARIANT_FLAGS;
+    static const CollocatedOps ops{&colloc_render_c<FL>, &colloc_render_fwd<FL>, &colloc_render_rev<FL>};
+    return &ops;
+}
+}  // namespace psdr_host

@@ -573,7 +573,7 @@ void fill_top(const psdr_scene_s *h, SceneView &sc) {
 int make_ctx(psdr_scene_s *h, const psdr_render_opts *o, int sampler, LaunchCtx &cx) {
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (!h->have_bvh) return fail("Input scene must be configured!");
-    if (o->integrator != PSDR_INTEGRATOR_FIELD && h->desc.num_emitters <= 0) return fail("No Emitter!");
+    if (o->integrator != PSDR_INTEGRATOR_FIELD && o->integrator != PSDR_INTEGRATOR_COLLOCATED && h->desc.num_emitters <= 0) return fail("No Emitter!");
     if (o->integrator == PSDR_INTEGRATOR_DIRECT && !(o->bsdf_samples >= 0 && o->light_samples >= 0 && o->bsdf_samples + o->light_samples > 0))
         return fail("DirectIntegrator: bsdf_samples + light_samples must be positive");
     cx.sc.d = h->desc; cx.sc.nodes = h->d_nodes; cx.sc.btris = h->d_btris; cx.sc.root = h->root;
@@ -980,6 +980,21 @@ const PathSedgeOps *path_sedge_of(const psdr_scene_s *h) {
         case 8: return path_sedge_ops_8();
         case 10: return path_sedge_ops_10();
         default: return path_sedge_ops_6();
+    }
+}
+// ... and for the kernels of psdr_collocated.hip
+const CollocatedOps *collocated_of(const psdr_scene_s *h) {
+    int fl = (h->desc.env_emitter >= 0 ? kSceneEnv : 0) | (h->has_rough ? kSceneRough : 0) | (h->n_blas > 0 ? kSceneForest : 0);
+    if (tiny_tables_ok(h)) fl |= kSceneTiny;
+    switch (fl) {
+        case 0: return collocated_ops_0();
+        case 1: return collocated_ops_1();
+        case 2: return collocated_ops_2();
+        case 3: return collocated_ops_3();
+        case 4: return collocated_ops_4();
+        case 8: return collocated_ops_8();
+        case 10: return collocated_ops_10();
+        default: return collocated_ops_6();
     }
 }
 }  // namespace psdr_host
@@ -1410,6 +1425,7 @@ int psdr_render_c(psdr_scene_t h, const psdr_render_opts *o, float *out_img, voi
     if (o->integrator == PSDR_INTEGRATOR_PATH) h->last_path_depth = o->max_depth;
     const long long WH = (long long) h->desc.width * h->desc.height;
     HIP_TRY(hipMemsetAsync(out_img, 0, sizeof(float) * WH * 3, s));
+    if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_c(h, o, out_img, s);
     return variant_of(h)->render_c(h, o, out_img, s);
 }
 
@@ -1422,6 +1438,7 @@ int psdr_render_d_fwd(psdr_scene_t h, const psdr_render_opts *o, int32_t K, cons
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
     if (K != 1 && K != 3) return fail("psdr_render_d_fwd: K must be 1 or 3");
+    if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s);          // interior + primary edges: no secondary-edge term
     if (int rc = variant_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s)) return rc;
     return path_sedge_of(h)->fwd(h, o, K, tangents, out_dimg, s);          // PSDR_FLAG_PATH_SEDGES (nothing without it)
 }
@@ -1439,6 +1456,7 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
     if (int rc = begin_call(h, s)) return rc;
     std::fill(std::begin(h->rev_layout), std::end(h->rev_layout), 0);
     h->rev_layout[8] = -1;                                                // (no camera launch)
+    if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_rev(h, o, adj_img, out_img, grads, s);
     if (int rc = variant_of(h)->render_rev(h, o, adj_img, out_img, grads, s)) return rc;
     return path_sedge_of(h)->rev(h, o, adj_img, grads, s);                 // PSDR_FLAG_PATH_SEDGES (nothing without it)
 }

@@ -364,6 +364,21 @@ const PathSedgeOps *path_sedge_ops_4();
 const PathSedgeOps *path_sedge_ops_6();
 const PathSedgeOps *path_sedge_ops_8();
 const PathSedgeOps *path_sedge_ops_10();
+// The CollocatedIntegrator (PSDR_INTEGRATOR_COLLOCATED, psdr_collocated.h) per flag set: psdr_collocated.hip, one more translation unit per set.  The C ABI picks
+// these entries for that integrator before the variant's own dispatch; render_c: the image has been zeroed
+struct CollocatedOps {
+    int (*render_c)(psdr_scene_s *h, const psdr_render_opts *o, float *img, hipStream_t s);
+    int (*render_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s);
+    int (*render_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, hipStream_t s);
+};
+const CollocatedOps *collocated_ops_0();
+const CollocatedOps *collocated_ops_1();
+const CollocatedOps *collocated_ops_2();
+const CollocatedOps *collocated_ops_3();
+const CollocatedOps *collocated_ops_4();
+const CollocatedOps *collocated_ops_6();
+const CollocatedOps *collocated_ops_8();
+const CollocatedOps *collocated_ops_10();
 // The lean twin of the K = 1 log-derivative camera kernel for flag set 8 (psdr_logd_lean.hip): launches it behind the gate kernels of run_camera and
 // sets *ran, or leaves *ran false -- option logd_park 0, or the parking columns do not fit six workgroups per CU (or a forced lds_budget) -- and
 // run_camera launches k_camera_logd.  cx: the launch context of run_camera (off_park is set on a copy).

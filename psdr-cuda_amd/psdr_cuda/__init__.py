@@ -10,6 +10,6 @@ from .core import (Object, RenderOption, Bitmap1fD, Bitmap3fD, DiscreteDistribut
                    SampleRecordC, SampleRecordD, PositionSampleC, PositionSampleD)
 from .scene import (BSDF, Diffuse, DiffuseBSDF, RoughConductor, RoughConductorBSDF, Emitter, AreaLight, EnvironmentMap,  # noqa: F401
                     Sensor, PerspectiveCamera, Mesh, Scene, PositionSample, BoundarySegSampleDirect)
-from .integrator import Integrator, FieldExtractionIntegrator, DirectIntegrator, PathTracer  # noqa: F401
+from .integrator import Integrator, FieldExtractionIntegrator, DirectIntegrator, PathTracer, CollocatedIntegrator  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

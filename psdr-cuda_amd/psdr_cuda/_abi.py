@@ -25,7 +25,7 @@ TRI_FACE_NORMALS = 0x40000000
 BSDF_DIFFUSE, BSDF_ROUGHCONDUCTOR = 0, 1
 SLOT_REFLECTANCE, SLOT_ALPHA_U, SLOT_ALPHA_V, SLOT_ETA, SLOT_K = range(5)
 CAM_SAMPLE_TO_CAMERA, CAM_TO_WORLD, CAM_WORLD_TO_SAMPLE, CAM_POS, CAM_DIR, CAM_INV_AREA = 0, 16, 32, 48, 51, 54
-INTEGRATOR_DIRECT, INTEGRATOR_PATH, INTEGRATOR_FIELD = 0, 1, 2
+INTEGRATOR_DIRECT, INTEGRATOR_PATH, INTEGRATOR_FIELD, INTEGRATOR_COLLOCATED = 0, 1, 2, 3
 FLAG_FUSED, FLAG_WAVEFRONT, FLAG_LITERAL_FORMS, FLAG_KEEP_RECORDS, FLAG_PATH_SEDGES = 1, 2, 4, 8, 16
 MAX_PATH_SEDGE_DEPTH = 8          # csrc/psdr_path_sedge.h kMaxPathSedgeDepth
 FIELDS = {"silhouette": 0, "position": 1, "depth": 2, "geoNormal": 3, "shNormal": 4, "uv": 5}

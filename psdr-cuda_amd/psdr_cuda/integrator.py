@@ -494,3 +494,107 @@ class PathTracer(Integrator):
         else:
             self._guide[sensor_id] = tuple(grids)
         return tuple(out)
+
+
+class _CollocatedNode:
+    """renderD of the CollocatedIntegrator: the unit-intensity render node (what the kernels compute) and the light's RGB intensity, which multiplies
+    image and derivative image per channel on the host.  enoki.forward sees eight inputs: the seven tables and the intensity."""
+
+    def __init__(self, unit, intensity):
+        self.unit, self.intensity = unit, intensity
+
+    def input_tensors(self):
+        return self.unit.input_tensors() + [self.intensity.t]
+
+    def render_forward(self, tangents):
+        d_unit = self.unit.render_forward(list(tangents[:-1]))          # one forward-mode launch: unit image and its derivative
+        unit, scale = self.unit.primal, self.intensity.t.detach().reshape(1, 3)
+        self.primal = unit * scale
+        d = d_unit * scale
+        if tangents[-1] is not None:
+            d = d + unit * tangents[-1].detach().reshape(1, 3)
+        return d
+
+    def render_primal(self):
+        """image = unit image x intensity, with autograd history: torch's product rule hands the adjoint image, scaled per channel, to the reverse
+        launch and the per-channel sum of adjoint x unit image to the intensity."""
+        unit, inputs = self.unit, self.unit.input_tensors()
+        with torch.enable_grad():
+            if any(t is not None and t.requires_grad for t in inputs):
+                img = _RenderFn.apply(unit, *inputs)
+            else:
+                with _decided(unit.collective):
+                    img = unit.integrator._render_c(unit.scene, unit.tb, unit.opts, unit.guide, interior_only=True).reshape(-1, 3)
+            return img * self.intensity.t.reshape(1, 3)
+
+    def release(self):
+        pass
+
+
+class _CollocatedImage(Vector3fD):
+    """What CollocatedIntegrator.renderD returns: rendered when first looked at, like _LazyImage (after enoki.forward the forward-mode launch has
+    produced the image already)."""
+
+    @classmethod
+    def _make(cls, node):
+        o = cls.__new__(cls)
+        o._node, o._t = node, None
+        return o
+
+    @property
+    def t(self):
+        if self._t is None:
+            primal = getattr(self._node, "primal", None)
+            self._t = primal if primal is not None else self._node.render_primal()
+        return self._t
+
+    @t.setter
+    def t(self, v):
+        self._t = v
+
+
+class CollocatedIntegrator(Integrator):
+    """A point light at the camera position (a camera flash), the capture configuration in which albedo and roughness maps are recovered from
+    photographs.  NOT in the reference snapshot: build-defined, like PathTracer.  For a camera ray with origin o that hits `its`
+
+        Li = intensity * f(its; wi = its.wi, wo = its.wi) / |its.p - o|^2          (0 on a miss)
+
+    with f the BSDF value, cosine included.  Emitters in the scene add nothing and a scene without any emitter is valid.  One ray per sample, no random
+    numbers beyond the film jitter.  renderD's geometry gradient is the interior and the primary-edge term, and that is all of it: a point the camera
+    sees is lit, so no shadow boundary is visible and scene.opts.sppse is ignored.
+
+    intensity: a float, three floats (RGB) or a Vector3fD; kept as the differentiable attribute m_intensity.  The kernels render unit intensity
+    (csrc/psdr_collocated.h); image, derivative image and adjoint image are scaled per channel here."""
+    _type_name = "CollocatedIntegrator"
+    _kind = _abi.INTEGRATOR_COLLOCATED
+
+    def __init__(self, intensity=1.0):
+        super().__init__()
+        if isinstance(intensity, Vector3fD):
+            psdr_assert(tuple(intensity.t.shape) == (1, 3), "intensity: one RGB triple expected")
+            self.m_intensity = intensity
+        else:
+            v = [float(x) for x in np.asarray(intensity, dtype=np.float64).reshape(-1)]
+            psdr_assert(len(v) in (1, 3), "intensity: a float or three floats expected")
+            self.m_intensity = Vector3fD(v * 3 if len(v) == 1 else v)
+
+    def renderC(self, scene, sensor_id=0):
+        img = super().renderC(scene, sensor_id)          # unit intensity (joins the image's all-reduce)
+        return Vector3fC._wrap(img.t * self.m_intensity.t.detach().reshape(1, 3).to(img.t.device))
+
+    def renderD(self, scene, sensor_id=0):
+        psdr_assert(scene.is_ready(), "Input scene must be configured!")
+        psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")
+        t0 = time.perf_counter()
+        tb = scene.tables(sensor_id, capacity=True)
+        opts = self._opts(scene, with_edges=True)
+        if not (scene._sensor_tables[sensor_id]["num_prim_edges"] > 0):
+            opts.sppe = opts.sppe_begin = opts.sppe_end = 0
+        img = _CollocatedImage._make(_CollocatedNode(_RenderNode(self, scene, sensor_id, tb, opts, None), self.m_intensity))
+        self._advance_rng(scene, opts)
+        ek.register_render_node(img)
+        if scene.opts.log_level:
+            img.t                                        # (the log line reports the render's time)
+            torch.cuda.synchronize()
+            self.log("Rendered in %g seconds." % (time.perf_counter() - t0))
+        return img
