@@ -4,6 +4,7 @@
     python examples/inverse_rendering.py albedo       # recover a wall colour (material parameter)
     python examples/inverse_rendering.py translation  # move an occluder back (geometry: all three terms)
     python examples/inverse_rendering.py envmap       # recover the environment map's pixels under a metal bunny
+    python examples/inverse_rendering.py shape        # recover a displaced sphere's vertices, one by one, through psdr_cuda.LargeSteps
 
 Needs an MI355X (the render path has no CPU fallback)."""
 import os
@@ -88,5 +89,59 @@ def envmap():
          lambda: "mean |map - truth| %.4f" % float(np.abs(env.radiance.data.numpy() - truth).mean()))
 
 
+def icosphere(level):
+    """unit icosphere: (vertices [V, 3], faces [F, 3])"""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [np.array(p, np.float64) for p in ((-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1))]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(level):
+        mid, nf = {}, []
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                v.append(v[a] + v[b])
+                mid[key] = len(v) - 1
+            return mid[key]
+        for a, b, c in f:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    v = np.array(v)
+    return v / np.linalg.norm(v, axis=1, keepdims=True), np.array(f, np.int32)
+
+
+def shape():
+    """Per-vertex shape optimisation.  Raw vertex gradients of a Monte Carlo boundary estimator tangle a mesh within a few Adam steps; the parameter is
+    therefore u = (I + lambda L) x (psdr_cuda.LargeSteps), the positions are recovered by one solve per step, warm-started from the previous step's, and
+    the backward pass turns the vertex gradient into (I + lambda L)^-1 g by a second solve."""
+    integ = psdr_cuda.DirectIntegrator(1, 1)
+    v, f = icosphere(3)
+
+    def scene(verts, spp, sppe=0, sppse=0):
+        sc = load("cbox_occluder", spp=spp, sppe=sppe, sppse=sppse)
+        sc.param_map["Mesh[id=occluder]"].set_geometry(verts, f)
+        return sc
+    ref = scene(v * 35.0, 128); ref.configure()
+    target = integ.renderC(ref).torch().clone()
+    # start: the sphere squeezed and dented
+    start = v * np.array([45.0, 25.0, 35.0]) * (1.0 + 0.15 * np.sin(4.0 * v[:, :1]))
+    sc = scene(start, 16, 16, 16)
+    mesh = sc.param_map["Mesh[id=occluder]"]
+    ls = psdr_cuda.LargeSteps(mesh, lmbda=19.0)
+    u = ls.to_differential(ek.detach(mesh.vertex_positions))
+    ek.set_requires_gradient(u)
+    truth = torch.as_tensor(v * 35.0, dtype=torch.float32, device="cuda")
+    state = {"x": None}
+
+    def apply():
+        x = ls.from_differential(u, x0=state["x"])
+        state["x"] = ek.detach(x)
+        mesh.vertex_positions = x
+    apply()
+    loop(sc, integ, target, [u], 1.0, 120, apply,
+         lambda: "mean vertex distance %.3f, %d CG iterations" % (float((state["x"].t - truth).norm(dim=1).mean()), ls.info()["iterations"]))
+
+
 if __name__ == "__main__":
-    {"albedo": albedo, "translation": translation, "envmap": envmap}[sys.argv[1] if len(sys.argv) > 1 else "albedo"]()
+    {"albedo": albedo, "translation": translation, "envmap": envmap, "shape": shape}[sys.argv[1] if len(sys.argv) > 1 else "albedo"]()

@@ -427,6 +427,41 @@ int psdr_geo_emitter_tables(int32_t M, const float *rows, int32_t row_stride, co
                             const float *radiance, const float *env_weight, float *mesh_area, float *emitter_f, float *emitter_pmf, float *emitter_cmf, float *face_pmf,
                             float *face_cmf, void *stream);
 
+/* ---- LargeSteps: u = (I + lambda L) x and x = (I + lambda L)^-1 b on vertex tables (csrc/psdr_smooth.hip) ----------------------
+   The parameterisation of "Large Steps in Inverse Rendering" (Nicolet, Jacobson, Jakob 2021) for per-vertex shape optimisation; the
+   reference has no counterpart.  L is the combinatorial Laplacian of the mesh's unique undirected edges: an edge shared by any number
+   of faces or repeated by a duplicated face counts once, an edge (a, a) of a degenerate face is dropped, a vertex no face uses has the
+   identity row.  Tables are [V][3] float, device, caller-owned.  The solve is conjugate gradients on the three columns in lockstep
+   (csrc/psdr_smooth.h): it stops when every column has ||r|| <= tol ||b|| or at max_iter; a column with ||b|| = 0 returns exact zeros.
+   A solve that does not converge is NOT an error (psdr_smooth_info reports it); non-finite input gives non-finite output after at most
+   max_iter iterations.  Two launch forms, chosen by the option "one_workgroup": 1 = the whole solve in one launch of one workgroup
+   (at most one_workgroup_limit vertices, else an error), 0 = two launches per iteration with every scalar on the device, -1 (default) =
+   by the vertex count.  Either form is enqueued on the caller's stream and never waits on the host; psdr_smooth_info is the one call
+   that waits.  The handle owns the adjacency and the work vectors: solves on one handle run one behind the other. */
+typedef struct psdr_smooth_s *psdr_smooth_t;
+typedef struct psdr_smooth_info_s {
+    int32_t iterations;             /* CG steps of the handle's last solve */
+    int32_t converged;              /* 1: every column met the tolerance */
+    int32_t form;                   /* 1 one workgroup, 0 multi launch, -1 no solve yet */
+    int32_t launches;               /* kernel launches the last solve enqueued */
+    float rel_residual[3];          /* ||r|| / ||b|| per column (of the recurrence; 0 for a zero column) */
+    int32_t one_workgroup_limit;    /* most vertices the one-workgroup form holds */
+    int32_t one_workgroup_default;  /* option -1: meshes up to this many vertices take it */
+    int32_t num_vertices;
+    int32_t num_entries;            /* directed entries of the adjacency = 2 x unique edges */
+    int32_t long_rows;              /* rows gathered by a whole wave (more than 64 neighbours) */
+} psdr_smooth_info_t;
+/* faces: HOST [F][3] int32; an index outside [0, V) is an error.  Builds and uploads the adjacency (CSR, rows sorted by column). */
+int psdr_smooth_create(int32_t V, int32_t F, const int32_t *faces, psdr_smooth_t *out);
+void psdr_smooth_destroy(psdr_smooth_t h);
+int psdr_smooth_set_option(psdr_smooth_t h, const char *name, int value);
+/* u = (I + lambda L) x; lambda >= 0; x and u must not alias. */
+int psdr_smooth_apply(psdr_smooth_t h, float lambda, const float *x, float *u, void *stream);
+/* x = (I + lambda L)^-1 b; x0 = the initial guess or NULL (zero); x0 may be x, b may not.  tol > 0, max_iter >= 1. */
+int psdr_smooth_solve(psdr_smooth_t h, float lambda, const float *b, const float *x0, float *x, float tol, int32_t max_iter, void *stream);
+/* Waits for the handle's last solve. */
+int psdr_smooth_info(psdr_smooth_t h, psdr_smooth_info_t *out);
+
 /* Gradient layout of the last psdr_render_d_rev on this handle (diagnostics: which destination each adjoint of the camera
    term went to; zeros before the first call).  out = {
      [0] texel words cached in LDS (0: global atomics), [1] emitter-radiance words cached, [2] environment-map words cached,

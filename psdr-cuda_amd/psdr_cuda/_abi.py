@@ -79,6 +79,15 @@ class Grads(C.Structure):
                 ("g_sec_edge", _fp), ("g_prim_edge", _fp), ("g_env_f", _fp)]
 
 
+class SmoothInfo(C.Structure):
+    """psdr_smooth_info_t"""
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("form", C.c_int32), ("launches", C.c_int32), ("rel_residual", C.c_float * 3),
+                ("one_workgroup_limit", C.c_int32), ("one_workgroup_default", C.c_int32), ("num_vertices", C.c_int32), ("num_entries", C.c_int32),
+                ("long_rows", C.c_int32)]
+
+
+SMOOTH_FORMS = {-1: "none", 0: "multi_launch", 1: "one_workgroup"}
+
 TANGENT_FIELDS = ("tri_info", "texels", "emitter_rad", "cam_to_world", "sec_edge", "prim_edge", "env_f")
 
 # every symbol include/psdr_hip.h declares (checked by tests/test_abi.py)
@@ -90,6 +99,7 @@ HIP_SYMBOLS = (
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
     "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
     "psdr_cube_sample_reuse", "psdr_sample_boundary_segment_direct",
+    "psdr_smooth_create", "psdr_smooth_destroy", "psdr_smooth_set_option", "psdr_smooth_apply", "psdr_smooth_solve", "psdr_smooth_info",
 )
 
 HIP_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libpsdr_hip.so")   # the in-tree build; the package reads NO environment variable
@@ -154,8 +164,15 @@ def load_hip():
     lib.psdr_geo_emitter_tables.argtypes = [i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.psdr_cube_sample_reuse.argtypes = [i32, C.POINTER(i32), vp, vp, C.c_float, i32, i32, vp, vp, vp]
     lib.psdr_sample_boundary_segment_direct.argtypes = [C.POINTER(SceneDesc), i32] + [vp] * 12
+    lib.psdr_smooth_create.argtypes = [i32, i32, vp, C.POINTER(vp)]
+    lib.psdr_smooth_destroy.argtypes = [vp]
+    lib.psdr_smooth_destroy.restype = None
+    lib.psdr_smooth_set_option.argtypes = [vp, C.c_char_p, C.c_int]
+    lib.psdr_smooth_apply.argtypes = [vp, C.c_float, vp, vp, vp]
+    lib.psdr_smooth_solve.argtypes = [vp, C.c_float, vp, vp, vp, C.c_float, i32, vp]
+    lib.psdr_smooth_info.argtypes = [vp, C.POINTER(SmoothInfo)]
     for name in HIP_SYMBOLS:
-        if name not in ("psdr_last_error", "psdr_version"):
+        if name not in ("psdr_last_error", "psdr_version", "psdr_smooth_destroy"):
             getattr(lib, name).restype = C.c_int
     sizes = (C.c_int32 * 4)()
     lib.psdr_abi_struct_sizes(sizes)
