@@ -1,79 +1,54 @@
 """Front-end of tests/hostcheck/hostcheck_collocated.cpp (the CollocatedIntegrator's estimator, csrc/psdr_collocated.h, run on the host) and the small scenes the
 CollocatedIntegrator's tests share."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
-import torch
 
+import hostlibs
 import psdr_cuda
-from helpers import ROOT, _grad_buffers, AD_KEYS
+from helpers import _grad_buffers, AD_KEYS
+from hostlibs import HC_DIR, cpu_desc, host_threads, tangents_struct
 from psdr_cuda import _abi
-from psdr_cuda.scene import make_desc
 
-HC_DIR = os.path.join(ROOT, "tests", "hostcheck")
-HC_SRC = os.path.join(HC_DIR, "hostcheck_collocated.cpp")
-HC_DEPS = [HC_SRC] + [os.path.join(ROOT, "psdr-cuda_amd", "csrc", f) for f in ("psdr_math.h", "psdr_device.h", "psdr_reverse.h", "psdr_collocated.h", "psdr_bvh_build.h")]
-_lib = None
+HC_DEPS = hostlibs.deps("collocated")          # (what tests/test_collocated_host.py's stand-alone program is stale against, besides its own source)
 
 
 def collocated_lib():
-    global _lib
-    if _lib is None:
-        so = os.path.join(HC_DIR, "libhostcheck_collocated.so")
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in HC_DEPS):
-            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", HC_SRC, "-o", so])
-        _lib = C.CDLL(so)
-    return _lib
+    return hostlibs.load("collocated")
 
 
 def colloc_opts(spp, sppe=0, rng_offset=(0, 0, 0), spp_range=None, sppe_range=None, sppse=0):
     return _abi.make_opts(integrator=_abi.INTEGRATOR_COLLOCATED, spp=spp, sppe=sppe, sppse=sppse, spp_range=spp_range, sppe_range=sppe_range, rng_offset=rng_offset)
 
 
-def _cpu_desc(tb):
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    desc, keep = make_desc(tbc, None, device="cpu")
-    return tbc, desc, keep
-
-
 def host_colloc_render(tb, opts, mode=0, tangents=None, nthreads=None):
     """renderC (mode 0: image) or forward mode, K = 1 (mode 1: image, derivative image) of the product code on the host, unit intensity."""
-    H = collocated_lib()
-    tbc, desc, keep = _cpu_desc(tb)
+    tbc, desc, keep = cpu_desc(tb)
     n = tb["width"] * tb["height"] * 3
     img, dimg = np.zeros(n, np.float32), np.zeros(n, np.float32)
-    tan = _abi.Tangents()
-    for k, t in (tangents or {}).items():
-        if t is not None:
-            t = t.detach().cpu().float().contiguous()
-            keep.append(t)
-            setattr(tan, "d_" + k, t.data_ptr())
-    rc = H.hostcheck_collocated_render(C.byref(desc), C.byref(opts), int(mode), C.byref(tan), C.c_void_p(img.ctypes.data), C.c_void_p(dimg.ctypes.data), nthreads or min(os.cpu_count(), 16))
+    tan = tangents_struct(tangents, keep)
+    rc = collocated_lib().hostcheck_collocated_render(C.byref(desc), C.byref(opts), int(mode), C.byref(tan), C.c_void_p(img.ctypes.data), C.c_void_p(dimg.ctypes.data), nthreads or host_threads())
     assert rc == 0, rc
     return (img.reshape(-1, 3), dimg.reshape(-1, 3)) if mode else img.reshape(-1, 3)
 
 
 def host_colloc_rev(tb, opts, adj, want=AD_KEYS):
     """Reverse mode on the host: (image, {table: gradient})."""
-    H = collocated_lib()
-    tbc, desc, keep = _cpu_desc(tb)
+    tbc, desc, keep = cpu_desc(tb)
     bufs, g = _grad_buffers(tbc, want)
     adj = np.ascontiguousarray(adj, dtype=np.float32).reshape(-1)
     img = np.zeros(adj.shape[0], np.float32)
-    rc = H.hostcheck_collocated_rev(C.byref(desc), C.byref(opts), C.c_void_p(adj.ctypes.data), C.c_void_p(img.ctypes.data), C.byref(g))
+    rc = collocated_lib().hostcheck_collocated_rev(C.byref(desc), C.byref(opts), C.c_void_p(adj.ctypes.data), C.c_void_p(img.ctypes.data), C.byref(g))
     assert rc == 0, rc
     return img.reshape(-1, 3), bufs
 
 
 def host_film_samples(tb, opts):
     """(sx, sy) of every camera slot of renderC, slot order (pixel-major), as the harness draws them: [W H nsp, 2]"""
-    H = collocated_lib()
-    tbc, desc, keep = _cpu_desc(tb)
+    tbc, desc, keep = cpu_desc(tb)
     n = tb["width"] * tb["height"] * (opts.spp_end - opts.spp_begin)
     out = np.zeros(2 * n, np.float32)
-    assert H.hostcheck_collocated_film_samples(C.byref(desc), C.byref(opts), C.c_void_p(out.ctypes.data)) == 0
+    assert collocated_lib().hostcheck_collocated_film_samples(C.byref(desc), C.byref(opts), C.c_void_p(out.ctypes.data)) == 0
     return out.reshape(-1, 2)
 
 

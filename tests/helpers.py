@@ -1,7 +1,6 @@
 """Shared helpers for the test-suite: scene set-up, oracle / hostcheck / GPU render front-ends."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import torch
@@ -10,6 +9,7 @@ import enoki as ek
 import psdr_cuda
 from enoki._array import _jvp_wrt
 from enoki.cuda_autodiff import Float32 as FloatD, Vector3f as Vector3fD, Matrix4f as Matrix4fD
+from hostlibs import cpu_desc, host_threads, load, tangents_struct
 from psdr_cuda import _abi
 from psdr_cuda.fixtures import scene_path
 
@@ -77,56 +77,24 @@ def tangents_wrt(tb, P):
 
 
 # ---------------------------------------------------------------- scratch / LDS / VGPR poison (tests/poison/poison.hip)
-_poison = None
-
-
 def poison_gpu(pattern, what=1):
     """Fill the queue's scratch arena (what & 1), the LDS of every CU (& 2), the VGPRs later waves inherit (& 4) with a bit pattern."""
-    global _poison
-    if _poison is None:
-        d = os.path.join(ROOT, "tests", "poison")
-        so, src = os.path.join(d, "libpoison.so"), os.path.join(d, "poison.hip")
-        if not os.path.exists(so) or os.path.getmtime(src) > os.path.getmtime(so):
-            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O1", "-fPIC", "-shared", src, "-o", so])
-        _poison = C.CDLL(so)
-    rc = _poison.poison_gpu(C.c_uint32(pattern), int(what))
+    rc = load("poison").poison_gpu(C.c_uint32(pattern), int(what))
     assert rc == 0, "poison_gpu failed (%d)" % rc
 
 
 # ---------------------------------------------------------------- hostcheck (product code on the CPU)
-_hostcheck = None
-
-
 def hostcheck_lib():
-    global _hostcheck
-    if _hostcheck is None:
-        d = os.path.join(ROOT, "tests", "hostcheck")
-        so = os.path.join(d, "libhostcheck.so")
-        src = os.path.join(d, "hostcheck.cpp")
-        hdrs = [os.path.join(ROOT, "psdr-cuda_amd", "csrc", f) for f in ("psdr_math.h", "psdr_device.h", "psdr_bvh_build.h")] + [os.path.join(d, "bvh4_host.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in [src] + hdrs):
-            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread",
-                                   src, "-o", so])
-        _hostcheck = C.CDLL(so)
-    return _hostcheck
+    return load("hostcheck")
 
 
 def host_render(tb, opts, mode=0, tangents=None, guide=None, nthreads=None):
-    H = hostcheck_lib()
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    if guide is not None:
-        guide = (guide[0], guide[1].cpu(), guide[2].cpu(), guide[3])
-    desc, keep = make_desc(tbc, guide, device="cpu")
+    tbc, desc, keep = cpu_desc(tb, guide)
     n = tb["width"] * tb["height"] * 3
     img, dimg = np.zeros(n, np.float32), np.zeros(n, np.float32)
-    tan = _abi.Tangents()
-    for k, t in (tangents or {}).items():
-        if t is not None:
-            t = t.detach().cpu().float().contiguous()
-            keep.append(t)
-            setattr(tan, "d_" + k, t.data_ptr())
-    rc = H.hostcheck_render(C.byref(desc), C.byref(opts), mode, C.byref(tan), C.c_void_p(img.ctypes.data),
-                            C.c_void_p(dimg.ctypes.data), nthreads or os.cpu_count())
+    tan = tangents_struct(tangents, keep)
+    rc = hostcheck_lib().hostcheck_render(C.byref(desc), C.byref(opts), mode, C.byref(tan), C.c_void_p(img.ctypes.data),
+                                          C.c_void_p(dimg.ctypes.data), nthreads or host_threads())
     assert rc == 0
     return (img.reshape(-1, 3), dimg.reshape(-1, 3)) if mode else img.reshape(-1, 3)
 
@@ -144,15 +112,11 @@ def _grad_buffers(tb, want):
 
 def host_render_rev(tb, opts, adj, want=AD_KEYS, guide=None):
     """Reverse mode of the product code on the host: returns (img, {table: gradient})."""
-    H = hostcheck_lib()
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    if guide is not None:
-        guide = (guide[0], guide[1].cpu(), guide[2].cpu(), guide[3])
-    desc, keep = make_desc(tbc, guide, device="cpu")
+    tbc, desc, keep = cpu_desc(tb, guide)
     bufs, g = _grad_buffers(tbc, want)
     adj = np.ascontiguousarray(adj, dtype=np.float32).reshape(-1)
     img = np.zeros(adj.shape[0], np.float32)
-    rc = H.hostcheck_render_rev(C.byref(desc), C.byref(opts), C.c_void_p(adj.ctypes.data), C.c_void_p(img.ctypes.data), C.byref(g))
+    rc = hostcheck_lib().hostcheck_render_rev(C.byref(desc), C.byref(opts), C.c_void_p(adj.ctypes.data), C.c_void_p(img.ctypes.data), C.byref(g))
     assert rc == 0
     return img.reshape(-1, 3), bufs
 
@@ -160,9 +124,7 @@ def host_render_rev(tb, opts, adj, want=AD_KEYS, guide=None):
 def host_render_rev_f64(tb, opts, adj, want=AD_KEYS):
     """Reverse mode of the product code on the host with every gradient entry accumulated in DOUBLE: returns (img, {table: (sum, abs_sum)}),
     sum = the entry's gradient, abs_sum = the sum of the magnitudes of the fp32 pieces it is made of (the scale an fp32 sum of the entry is judged by)."""
-    H = hostcheck_lib()
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    desc, keep = make_desc(tbc, None, device="cpu")
+    tbc, desc, keep = cpu_desc(tb)
     sums, abss = (C.c_void_p * 7)(), (C.c_void_p * 7)()
     out = {}
     for i, name in enumerate(_abi.TANGENT_FIELDS):
@@ -173,7 +135,7 @@ def host_render_rev_f64(tb, opts, adj, want=AD_KEYS):
         sums[i], abss[i] = out[name][0].ctypes.data, out[name][1].ctypes.data
     adj = np.ascontiguousarray(adj, dtype=np.float32).reshape(-1)
     img = np.zeros(adj.shape[0], np.float32)
-    rc = H.hostcheck_render_rev_f64(C.byref(desc), C.byref(opts), C.c_void_p(adj.ctypes.data), C.c_void_p(img.ctypes.data), sums, abss)
+    rc = hostcheck_lib().hostcheck_render_rev_f64(C.byref(desc), C.byref(opts), C.c_void_p(adj.ctypes.data), C.c_void_p(img.ctypes.data), sums, abss)
     assert rc == 0
     return img.reshape(-1, 3), out
 

@@ -2,62 +2,14 @@
 // functions) on the host, sample by sample, so that `-m "not gpu"` tests can compare it with the
 // oracle where no GPU exists.  It is never imported by the psdr_cuda package and is not a fallback:
 // the render path (libpsdr_hip.so) only ever executes these functions inside HIP kernels.
-#include "../../psdr-cuda_amd/csrc/psdr_bvh_build.h"
-#include "../../psdr-cuda_amd/csrc/psdr_reverse.h"
+#include "host_common.h"
 #include "bvh4_host.h"
-
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-using namespace psdr;
-
-namespace {
-struct HostScene {
-    SceneView sc{};
-    Builder b;
-};
-bool setup(HostScene &hs, const psdr_scene_desc *d) {
-    hs.sc.d = *d;
-    if (!hs.sc.d.env_f) hs.sc.d.env_emitter = -1;
-    int32_t root = 0;
-    if (hs.b.run(d->tri_info, d->num_tris, root)) return false;
-    hs.sc.nodes = hs.b.nodes.data(); hs.sc.btris = hs.b.btris.data(); hs.sc.root = root;
-    // tiny scenes take the all-triangles path of closest_hit, as psdr_bvh_build arranges on the device
-    const char *e = std::getenv("PSDR_TINY_SCENE");
-    if (d->num_tris <= kTinyTris && !(e && std::atoi(e) == 0)) {
-        std::vector<float4> prims;
-        pack_tiny_prims(hs.b.btris, prims);
-        hs.sc.n_tiny = tiny_plane_form(prims, hs.sc.tiny, hs.sc.tiny_meta, &hs.sc.aa_cnt);
-        // SceneView::emit_rows as psdr_bvh_build sets it (the estimators' emitter pre-test; the host check's TangentView flags carry neither kSceneTiny nor
-        // kSceneForest, so the estimators here do not USE it -- hostcheck_emitter_rows hands it to the tests)
-        std::vector<char> is_em((size_t) d->num_tris, 0);
-        for (int e = 0; e < d->num_emitters && d->emitter_i; ++e) {
-            const int32_t *ei = d->emitter_i + (size_t) e * PSDR_EMITTER_I_STRIDE;
-            for (int f = 0; f < ei[2]; ++f) if (ei[1] + f >= 0 && ei[1] + f < d->num_tris) is_em[(size_t) (ei[1] + f)] = 1;
-        }
-        hs.sc.emit_rows = tiny_emitter_rows(hs.sc.tiny_meta, hs.sc.n_tiny, hs.sc.aa_cnt, is_em);
-    }
-    return true;
-}
-template <class F> void pfor(long long n, int nt, F f) {
-    std::vector<std::thread> th;
-    long long chunk = (n + nt - 1) / nt;
-    for (int t = 0; t < nt; ++t) {
-        long long a = t * chunk, b = std::min(n, a + chunk);
-        if (a >= b) break;
-        th.emplace_back([=] { f(a, b, t); });
-    }
-    for (auto &x : th) x.join();
-}
-}  // namespace
 
 extern "C" {
 
 int hostcheck_trace(const psdr_scene_desc *d, int m, const float *o, const float *dir, int *tri, float *u, float *v) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     TraversalStack st;
     for (int i = 0; i < m; ++i) {
         Hit h = closest_hit(hs.sc, st, Vec3f{o[3 * i], o[3 * i + 1], o[3 * i + 2]}, Vec3f{dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]}, INFINITY);
@@ -69,7 +21,7 @@ int hostcheck_trace(const psdr_scene_desc *d, int m, const float *o, const float
 // the same search restricted to the rows a per-ray mask names (closest_hit MASKED: what the light rays of a scene without a tree run with SceneView::occ)
 int hostcheck_trace_rows(const psdr_scene_desc *d, int m, const float *o, const float *dir, const uint32_t *rows, int *tri, float *u, float *v, float *t) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     if (hs.sc.n_tiny <= 0) return 2;
     TraversalStack st;
     for (int i = 0; i < m; ++i) {
@@ -81,7 +33,7 @@ int hostcheck_trace_rows(const psdr_scene_desc *d, int m, const float *o, const 
 
 int hostcheck_emitter_rows(const psdr_scene_desc *d, uint32_t *rows) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     *rows = hs.sc.emit_rows;
     return 0;
 }
@@ -89,7 +41,7 @@ int hostcheck_emitter_rows(const psdr_scene_desc *d, uint32_t *rows) {
 // rows in use and slab-form slots per axis of a tiny scene's primitive list (tiny_plane_form)
 int hostcheck_tiny_layout(const psdr_scene_desc *d, int *out) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     out[0] = hs.sc.n_tiny; out[1] = hs.sc.aa_cnt & 255; out[2] = (hs.sc.aa_cnt >> 8) & 255; out[3] = hs.sc.aa_cnt >> 16;
     return 0;
 }
@@ -98,7 +50,7 @@ int hostcheck_tiny_layout(const psdr_scene_desc *d, int *out) {
 // row of `tiny` that holds the triangle; emitter triangles from the caller's emitter_i table
 int hostcheck_occluder_rows(const psdr_scene_desc *d, uint32_t *occ_out, int *row_of_tri) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     if (d->num_tris > kTinyTris) return 2;
     std::vector<float4> prims;
     std::vector<int> row_of_prim;
@@ -133,13 +85,13 @@ int hostcheck_bvh4(const float *rows, const int32_t *tri_mesh, int T, int num_me
 int hostcheck_render(const psdr_scene_desc *d, const psdr_render_opts *o, int mode, const psdr_tangents *tan, float *img, float *dimg,
                      int nthreads) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     hs.sc.literal_forms = (o->flags & PSDR_FLAG_LITERAL_FORMS) ? 1 : 0;
     const int W = d->width, H = d->height;
     const long long WH = (long long) W * H;
     const size_t n3 = (size_t) WH * 3;
     nthreads = std::max(1, nthreads);
-    std::vector<std::vector<double>> acc(nthreads, std::vector<double>(n3, 0.0)), dacc(nthreads, std::vector<double>(mode ? n3 : 0, 0.0));
+    ThreadImages acc(nthreads, n3), dacc(nthreads, mode ? n3 : 0);
     LiParams lp{o->integrator, o->bsdf_samples, o->light_samples, o->max_depth, o->hide_emitters, o->field};
     TangentView<1, kSceneAll> tv1; tv1.t[0] = tan ? *tan : psdr_tangents{};
     const TangentView<0, kSceneAll> tv0{};   // the host check always carries the env-map and rough-conductor code
@@ -196,18 +148,14 @@ int hostcheck_render(const psdr_scene_desc *d, const psdr_render_opts *o, int mo
             }
         });
     }
-    for (size_t i = 0; i < n3; ++i) {
-        double s = 0, ds = 0;
-        for (int t = 0; t < nthreads; ++t) { s += acc[t][i]; if (mode) ds += dacc[t][i]; }
-        img[i] = (float) s;
-        if (mode && dimg) dimg[i] = (float) ds;
-    }
+    acc.reduce(img);
+    if (mode && dimg) dacc.reduce(dimg);
     return 0;
 }
 
 int hostcheck_guide(const psdr_scene_desc *d, const int *reso, int nrounds, float *mass, int nthreads) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     hs.sc.d.guide_cmf = nullptr; hs.sc.d.num_guide_cells = 0;
     const long long cells = (long long) reso[0] * reso[1] * reso[2], n = cells * reso[3];
     std::vector<double> m(cells, 0.0);
@@ -239,24 +187,11 @@ int hostcheck_guide(const psdr_scene_desc *d, const int *reso, int nrounds, floa
 }
 
 namespace {
-struct HostSink {
-    static constexpr int flags = kSceneAll;
-    static constexpr bool has_env = true;
-    psdr_grads g;
-    void add_env(int w, float v) const { put(g.g_env_f, w, v); }
-    static void put(float *b, size_t i, float v) { if (b && v != 0.f && std::isfinite(v)) b[i] += v; }
-    void add_tri(int tri, int word, float v) const { put(g.g_tri_info, (size_t) tri * PSDR_TRI_STRIDE + word, v); }
-    void add_texel(int idx, float v) const { put(g.g_texels, idx, v); }
-    void add_rad(int e, int c, float v) const { put(g.g_emitter_rad, (size_t) e * 3 + c, v); }
-    void add_cam(int w, float v) const { put(g.g_cam_to_world, w, v); }
-    void add_sedge(int e, int w, float v) const { put(g.g_sec_edge, (size_t) e * PSDR_SEDGE_STRIDE + w, v); }
-    void add_pedge(int e, int w, float v) const { put(g.g_prim_edge, (size_t) e * PSDR_PEDGE_STRIDE + w, v); }
-};
 // The same sample loop for any sink; geo: the camera kernels with geometric adjoints (a triangle or camera table wanted)
 template <class Sink>
 int render_rev_host(const psdr_scene_desc *d, const psdr_render_opts *o, const float *adj, float *img, Sink &sink, bool geo) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     const int W = d->width, H = d->height;
     const long long WH = (long long) W * H;
     LiParams lp{o->integrator, o->bsdf_samples, o->light_samples, o->max_depth, o->hide_emitters, o->field};

@@ -3,71 +3,19 @@
 // integrator).  A library of its own (libhostcheck_collocated.so), as hostcheck_path_sedge.cpp is for its header.  Never imported by the psdr_cuda package and
 // not a fallback: the render path only ever executes these functions inside HIP kernels.  tests/hostcheck/collocated_san.cpp includes this file into a
 // stand-alone program for the host sanitizers.
-#include "../../psdr-cuda_amd/csrc/psdr_bvh_build.h"
+#include "host_common.h"
 #include "../../psdr-cuda_amd/csrc/psdr_collocated.h"
-
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-using namespace psdr;
-
-namespace {
-struct HostScene {
-    SceneView sc{};
-    Builder b;
-};
-// as hostcheck.cpp sets a scene up: one tree, or the all-primitives path of closest_hit for a tiny scene
-bool setup(HostScene &hs, const psdr_scene_desc *d) {
-    hs.sc.d = *d;
-    if (!hs.sc.d.env_f) hs.sc.d.env_emitter = -1;
-    int32_t root = 0;
-    if (hs.b.run(d->tri_info, d->num_tris, root)) return false;
-    hs.sc.nodes = hs.b.nodes.data(); hs.sc.btris = hs.b.btris.data(); hs.sc.root = root;
-    const char *e = std::getenv("PSDR_TINY_SCENE");
-    if (d->num_tris <= kTinyTris && !(e && std::atoi(e) == 0)) {
-        std::vector<float4> prims;
-        pack_tiny_prims(hs.b.btris, prims);
-        hs.sc.n_tiny = tiny_plane_form(prims, hs.sc.tiny, hs.sc.tiny_meta, &hs.sc.aa_cnt);
-    }
-    return true;
-}
-template <class F> void pfor(long long n, int nt, F f) {
-    std::vector<std::thread> th;
-    long long chunk = (n + nt - 1) / nt;
-    for (int t = 0; t < nt; ++t) {
-        long long a = t * chunk, b = std::min(n, a + chunk);
-        if (a >= b) break;
-        th.emplace_back([=] { f(a, b, t); });
-    }
-    for (auto &x : th) x.join();
-}
-struct HostSink {
-    static constexpr int flags = kSceneAll;
-    static constexpr bool has_env = true;
-    psdr_grads g;
-    static void put(float *b, size_t i, float v) { if (b && v != 0.f && std::isfinite(v)) b[i] += v; }
-    void add_env(int w, float v) const { put(g.g_env_f, w, v); }
-    void add_tri(int tri, int word, float v) const { put(g.g_tri_info, (size_t) tri * PSDR_TRI_STRIDE + word, v); }
-    void add_texel(int idx, float v) const { put(g.g_texels, idx, v); }
-    void add_rad(int e, int c, float v) const { put(g.g_emitter_rad, (size_t) e * 3 + c, v); }
-    void add_cam(int w, float v) const { put(g.g_cam_to_world, w, v); }
-    void add_sedge(int e, int w, float v) const { put(g.g_sec_edge, (size_t) e * PSDR_SEDGE_STRIDE + w, v); }
-    void add_pedge(int e, int w, float v) const { put(g.g_prim_edge, (size_t) e * PSDR_PEDGE_STRIDE + w, v); }
-};
-}  // namespace
 
 extern "C" {
 
 // mode 0: renderC (unit intensity); mode 1: renderD forward (K = 1), interior + primary edges.  Per-thread images in double, summed in thread order.
 int hostcheck_collocated_render(const psdr_scene_desc *d, const psdr_render_opts *o, int mode, const psdr_tangents *tan, float *img, float *dimg, int nthreads) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     const long long WH = (long long) d->width * d->height;
     const size_t n3 = (size_t) WH * 3;
     nthreads = std::max(1, nthreads);
-    std::vector<std::vector<double>> acc(nthreads, std::vector<double>(n3, 0.0)), dacc(nthreads, std::vector<double>(mode ? n3 : 0, 0.0));
+    ThreadImages acc(nthreads, n3), dacc(nthreads, mode ? n3 : 0);
     TangentView<1, kSceneAll> tv1; tv1.t[0] = tan ? *tan : psdr_tangents{};
     const TangentView<0, kSceneAll> tv0{};
     const int nsp = o->spp_end - o->spp_begin;
@@ -103,19 +51,15 @@ int hostcheck_collocated_render(const psdr_scene_desc *d, const psdr_render_opts
             }
         });
     }
-    for (size_t i = 0; i < n3; ++i) {
-        double s = 0, ds = 0;
-        for (int t = 0; t < nthreads; ++t) { s += acc[t][i]; if (mode) ds += dacc[t][i]; }
-        img[i] = (float) s;
-        if (mode && dimg) dimg[i] = (float) ds;
-    }
+    acc.reduce(img);
+    if (mode && dimg) dacc.reduce(dimg);
     return 0;
 }
 
 // reverse mode: the gradient tables `grads` names (zeroed by the caller), and the image if img is not null
 int hostcheck_collocated_rev(const psdr_scene_desc *d, const psdr_render_opts *o, const float *adj, float *img, const psdr_grads *grads) {
     HostScene hs;
-    if (!setup(hs, d)) return 1;
+    if (!setup(hs, d, Grid::keep)) return 1;
     HostSink sink; sink.g = *grads;
     const bool geo = grads->g_tri_info != nullptr || grads->g_cam_to_world != nullptr;
     const long long WH = (long long) d->width * d->height;

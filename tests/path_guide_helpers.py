@@ -1,30 +1,21 @@
 """Front-end of tests/hostcheck/hostcheck_path_guide.cpp: the guided secondary-edge term of the PathTracer and the guiding-grid build of either segment
 (csrc/psdr_path_sedge.h) run on the host, and what the CPU and GPU tests of the grids share."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import torch
 
-from helpers import ROOT, _grad_buffers, AD_KEYS
+import hostlibs
+from helpers import _grad_buffers, AD_KEYS
+from hostlibs import HC_DIR, cpu_desc, host_threads, tangents_struct
 from psdr_cuda import _abi
-from psdr_cuda.scene import make_desc
 
-_lib = None
-HC_DIR = os.path.join(ROOT, "tests", "hostcheck")
-HC_SRC = os.path.join(HC_DIR, "hostcheck_path_guide.cpp")
-HC_DEPS = [HC_SRC] + [os.path.join(ROOT, "psdr-cuda_amd", "csrc", f) for f in ("psdr_math.h", "psdr_device.h", "psdr_reverse.h", "psdr_path_sedge.h", "psdr_bvh_build.h")]
+HC_SRC = hostlibs.source("path_guide")
+HC_DEPS = hostlibs.deps("path_guide")          # (what tests/test_path_guide_host.py's stand-alone program is stale against)
 
 
 def path_guide_lib():
-    global _lib
-    if _lib is None:
-        so = os.path.join(HC_DIR, "libhostcheck_path_guide.so")
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in HC_DEPS):
-            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", HC_SRC, "-o", so])
-        _lib = C.CDLL(so)
-    return _lib
+    return hostlibs.load("path_guide")
 
 
 def make_grid(reso, mass):
@@ -44,11 +35,6 @@ def synthetic_grid(reso=(8, 4, 4)):
     return make_grid(reso, 1.0 + 3.0 * (c % 2))
 
 
-def _desc(tb, grid_a):
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    return tbc, make_desc(tbc, grid_a, device="cpu")
-
-
 def _grid_b_args(grid_b, keep):
     if grid_b is None:
         return None, None, None, C.c_float(0.0)
@@ -60,49 +46,40 @@ def _grid_b_args(grid_b, keep):
 
 def host_path_guide_fwd(tb, opts, tangents, grid_a=None, grid_b=None, seg=3, walk=1, nthreads=None):
     """Forward mode (K = 1) on the host: the derivative image of the guided secondary-edge term alone."""
-    H = path_guide_lib()
-    tbc, (desc, keep) = _desc(tb, grid_a)
+    tbc, desc, keep = cpu_desc(tb, grid_a)
     dimg = np.zeros(tb["width"] * tb["height"] * 3, np.float32)
-    tan = _abi.Tangents()
-    for k, t in (tangents or {}).items():
-        if t is not None:
-            t = t.detach().cpu().float().contiguous()
-            keep.append(t)
-            setattr(tan, "d_" + k, t.data_ptr())
-    rc = H.hostcheck_path_guide_fwd(C.byref(desc), C.byref(opts), int(seg), int(walk), *_grid_b_args(grid_b, keep), C.byref(tan), C.c_void_p(dimg.ctypes.data),
-                                    nthreads or os.cpu_count())
+    tan = tangents_struct(tangents, keep)
+    rc = path_guide_lib().hostcheck_path_guide_fwd(C.byref(desc), C.byref(opts), int(seg), int(walk), *_grid_b_args(grid_b, keep), C.byref(tan), C.c_void_p(dimg.ctypes.data),
+                                                   nthreads or host_threads())
     assert rc == 0, rc
     return dimg.reshape(-1, 3)
 
 
 def host_path_guide_rev(tb, opts, adj, grid_a=None, grid_b=None, want=AD_KEYS, seg=3, walk=1):
     """Reverse mode on the host: {table: gradient} of the guided secondary-edge term alone."""
-    H = path_guide_lib()
-    tbc, (desc, keep) = _desc(tb, grid_a)
+    tbc, desc, keep = cpu_desc(tb, grid_a)
     bufs, g = _grad_buffers(tbc, want)
     adj = np.ascontiguousarray(adj, dtype=np.float32).reshape(-1)
-    rc = H.hostcheck_path_guide_rev(C.byref(desc), C.byref(opts), int(seg), int(walk), *_grid_b_args(grid_b, keep), C.c_void_p(adj.ctypes.data), C.byref(g))
+    rc = path_guide_lib().hostcheck_path_guide_rev(C.byref(desc), C.byref(opts), int(seg), int(walk), *_grid_b_args(grid_b, keep), C.c_void_p(adj.ctypes.data), C.byref(g))
     assert rc == 0, rc
     return bufs
 
 
 def host_path_guide_survivors(tb, opts, grid_a=None, grid_b=None):
     """(survivors of segment A's filter, of segment B's, slots) under the grids, on the host"""
-    H = path_guide_lib()
-    tbc, (desc, keep) = _desc(tb, grid_a)
+    tbc, desc, keep = cpu_desc(tb, grid_a)
     out = (C.c_longlong * 3)()
-    rc = H.hostcheck_path_guide_survivors(C.byref(desc), C.byref(opts), *_grid_b_args(grid_b, keep), out)
+    rc = path_guide_lib().hostcheck_path_guide_survivors(C.byref(desc), C.byref(opts), *_grid_b_args(grid_b, keep), out)
     assert rc == 0, rc
     return int(out[0]), int(out[1]), int(out[2])
 
 
 def host_path_guide_mass(tb, opts, segment, reso, nrounds, walk=1, nthreads=None):
     """psdr_path_guide_build on the host: the mass of segment 1 (A) or 2 (B) on reso [4]"""
-    H = path_guide_lib()
-    tbc, (desc, keep) = _desc(tb, None)
+    tbc, desc, keep = cpu_desc(tb)
     mass = np.zeros(int(reso[0]) * int(reso[1]) * int(reso[2]), np.float32)
-    rc = H.hostcheck_path_guide_mass(C.byref(desc), C.byref(opts), int(segment), int(walk), (C.c_int32 * 4)(*[int(r) for r in reso]), int(nrounds),
-                                     C.c_void_p(mass.ctypes.data), nthreads or os.cpu_count())
+    rc = path_guide_lib().hostcheck_path_guide_mass(C.byref(desc), C.byref(opts), int(segment), int(walk), (C.c_int32 * 4)(*[int(r) for r in reso]), int(nrounds),
+                                                    C.c_void_p(mass.ctypes.data), nthreads or host_threads())
     assert rc == 0, rc
     return mass
 

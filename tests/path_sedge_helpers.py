@@ -1,29 +1,15 @@
 """Front-end of tests/hostcheck/hostcheck_path_sedge.cpp: the PathTracer's secondary-edge term (csrc/psdr_path_sedge.h) run on the host."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
-import torch
 
-from helpers import ROOT, _grad_buffers, AD_KEYS
+from helpers import _grad_buffers, AD_KEYS
+from hostlibs import cpu_desc, host_threads, load, tangents_struct
 from psdr_cuda import _abi
-from psdr_cuda.scene import make_desc
-
-_lib = None
 
 
 def path_sedge_lib():
-    global _lib
-    if _lib is None:
-        d = os.path.join(ROOT, "tests", "hostcheck")
-        so, src = os.path.join(d, "libhostcheck_path_sedge.so"), os.path.join(d, "hostcheck_path_sedge.cpp")
-        csrc = os.path.join(ROOT, "psdr-cuda_amd", "csrc")
-        hdrs = [os.path.join(csrc, f) for f in ("psdr_math.h", "psdr_device.h", "psdr_reverse.h", "psdr_path_sedge.h", "psdr_bvh_build.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in [src] + hdrs):
-            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", src, "-o", so])
-        _lib = C.CDLL(so)
-    return _lib
+    return load("path_sedge")
 
 
 def path_opts(max_depth, sppse, rng_offset=(0, 0, 0), sppse_range=None, spp=0, sppe=0):
@@ -33,40 +19,29 @@ def path_opts(max_depth, sppse, rng_offset=(0, 0, 0), sppse_range=None, spp=0, s
 
 def host_path_sedge_fwd(tb, opts, tangents, seg=3, walk=1, nthreads=None):
     """Forward mode (K = 1) on the host: the derivative image of the secondary-edge term alone."""
-    H = path_sedge_lib()
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    desc, keep = make_desc(tbc, None, device="cpu")
+    tbc, desc, keep = cpu_desc(tb)
     dimg = np.zeros(tb["width"] * tb["height"] * 3, np.float32)
-    tan = _abi.Tangents()
-    for k, t in (tangents or {}).items():
-        if t is not None:
-            t = t.detach().cpu().float().contiguous()
-            keep.append(t)
-            setattr(tan, "d_" + k, t.data_ptr())
-    rc = H.hostcheck_path_sedge_fwd(C.byref(desc), C.byref(opts), int(seg), int(walk), C.byref(tan), C.c_void_p(dimg.ctypes.data), nthreads or os.cpu_count())
+    tan = tangents_struct(tangents, keep)
+    rc = path_sedge_lib().hostcheck_path_sedge_fwd(C.byref(desc), C.byref(opts), int(seg), int(walk), C.byref(tan), C.c_void_p(dimg.ctypes.data), nthreads or host_threads())
     assert rc == 0, rc
     return dimg.reshape(-1, 3)
 
 
 def host_path_sedge_rev(tb, opts, adj, want=AD_KEYS, seg=3, walk=1):
     """Reverse mode on the host: {table: gradient} of the secondary-edge term alone."""
-    H = path_sedge_lib()
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    desc, keep = make_desc(tbc, None, device="cpu")
+    tbc, desc, keep = cpu_desc(tb)
     bufs, g = _grad_buffers(tbc, want)
     adj = np.ascontiguousarray(adj, dtype=np.float32).reshape(-1)
-    rc = H.hostcheck_path_sedge_rev(C.byref(desc), C.byref(opts), int(seg), int(walk), C.c_void_p(adj.ctypes.data), C.byref(g))
+    rc = path_sedge_lib().hostcheck_path_sedge_rev(C.byref(desc), C.byref(opts), int(seg), int(walk), C.c_void_p(adj.ctypes.data), C.byref(g))
     assert rc == 0, rc
     return bufs
 
 
 def host_path_sedge_survivors(tb, opts):
     """(survivors of segment A's filter, of segment B's, slots) on the host"""
-    H = path_sedge_lib()
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    desc, keep = make_desc(tbc, None, device="cpu")
+    tbc, desc, keep = cpu_desc(tb)
     out = (C.c_longlong * 3)()
-    rc = H.hostcheck_path_sedge_survivors(C.byref(desc), C.byref(opts), out)
+    rc = path_sedge_lib().hostcheck_path_sedge_survivors(C.byref(desc), C.byref(opts), out)
     assert rc == 0, rc
     return int(out[0]), int(out[1]), int(out[2])
 

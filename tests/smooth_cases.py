@@ -9,9 +9,10 @@ import os
 
 import numpy as np
 
-HC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMOOTH_H = os.path.join(ROOT, "psdr-cuda_amd", "csrc", "psdr_smooth.h")
+import hostlibs
+from hostlibs import HC_DIR, ROOT
+
+SMOOTH_H = os.path.join(hostlibs.CSRC, "psdr_smooth.h")
 BOUND = 5e-5
 TOL = 1e-6
 LAMBDAS = (1.0, 10.0, 100.0)
@@ -154,22 +155,13 @@ def rhs(name, lam):
 
 
 # ---------------------------------------------------------------- the host harness
-_lib = None
-
-
 def host_lib():
-    global _lib
-    if _lib is None:
-        path = os.path.join(HC_DIR, "libhostcheck_smooth.so")
-        if not os.path.exists(path):
-            raise RuntimeError("libhostcheck_smooth.so not built: run build() of __graft_entry__.py")
-        lib = C.CDLL(path)
-        vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-        lib.hostcheck_smooth_csr.argtypes = [i32, i32, vp, vp, vp, i32, vp, C.c_char_p, i32]
-        lib.hostcheck_smooth_apply.argtypes = [i32, i32, vp, f32, vp, vp]
-        lib.hostcheck_smooth_solve.argtypes = [i32, i32, vp, f32, vp, vp, vp, f32, i32, vp, vp]
-        _lib = lib
-    return _lib
+    lib = hostlibs.load("smooth")
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    lib.hostcheck_smooth_csr.argtypes = [i32, i32, vp, vp, vp, i32, vp, C.c_char_p, i32]
+    lib.hostcheck_smooth_apply.argtypes = [i32, i32, vp, f32, vp, vp]
+    lib.hostcheck_smooth_solve.argtypes = [i32, i32, vp, f32, vp, vp, vp, f32, i32, vp, vp]
+    return lib
 
 
 def _faces(faces):

@@ -1,7 +1,6 @@
 """The CollocatedIntegrator's estimator (csrc/psdr_collocated.h: a point light at the camera, Li = f(wi, wi) / r^2) on the HOST: the product's PSDR_HD functions
 run slot by slot by tests/hostcheck/hostcheck_collocated.cpp.  The reference snapshot has no such integrator and the oracle is not extended, so the estimator is
 pinned on closed forms, on the second oracle's BSDF values, on forward = reverse and on AD against finite differences of its own renderC."""
-import ctypes as C
 import os
 import subprocess
 
@@ -13,8 +12,8 @@ import oracle
 import torch_oracle as to
 from collocated_helpers import (DIFFUSE, HC_DEPS, HC_DIR, ROUGH, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, quad_xml, xml_scene)
 from helpers import dot_tables, load_scene, random_tangents, rel_l2, tangents_wrt
+from hostlibs import cpu_desc, write_tables_file
 from psdr_cuda import _abi
-from psdr_cuda.scene import make_desc
 
 RES, SPP = 16, 4
 
@@ -215,26 +214,9 @@ def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
     o = colloc_opts(spp, sppe, rng_offset=(1, 2, 0))
     tan = random_tangents(tb, ["tri_info", "texels", "prim_edge"], seed=3)
     adj = np.random.default_rng(4).random((res * res, 3)).astype(np.float32)
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    desc, keep = make_desc(tbc, None, device="cpu")
-    by_ptr = {t.data_ptr(): t for t in keep}
+    tbc, desc, keep = cpu_desc(tb)
     path = str(tmp_path / "tables.bin")
-    with open(path, "wb") as f:
-        f.write(np.int64(C.sizeof(desc)).tobytes())
-        f.write(bytes(desc))
-        recs = []
-        for fname, ftype in desc._fields_:
-            if ftype is C.c_void_p and getattr(desc, fname):
-                recs.append((getattr(type(desc), fname).offset, by_ptr[getattr(desc, fname)]))
-        f.write(np.int64(len(recs)).tobytes())
-        for off, t in recs:
-            raw = t.numpy().tobytes()
-            f.write(np.array([off, len(raw)], np.int64).tobytes())
-            f.write(raw)
-        f.write(bytes(o))
-        for n in ("tri_info", "texels", "prim_edge"):
-            f.write(tan[n].detach().cpu().numpy().astype(np.float32).tobytes())
-        f.write(adj.tobytes())
+    write_tables_file(path, desc, keep, o, *[tan[n].detach().cpu().numpy().astype(np.float32) for n in ("tri_info", "texels", "prim_edge")], adj)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([exe, path], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-3000:])

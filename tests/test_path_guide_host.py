@@ -15,6 +15,7 @@ import torch
 
 import oracle
 from helpers import dot_tables, host_render, hostcheck_lib, load_scene, random_tangents, rel_l2, tangents_wrt
+from hostlibs import cpu_desc, write_tables_file
 from path_guide_helpers import (HC_DEPS, HC_DIR, HC_SRC, host_path_guide_fwd, host_path_guide_mass, host_path_guide_rev, host_path_guide_survivors, make_grid,
                                 one_cell_grid, synthetic_grid)
 from path_sedge_helpers import SCENARIOS, host_path_sedge_fwd, host_path_sedge_rev, host_path_sedge_survivors, path_opts, scenario_scene
@@ -166,30 +167,10 @@ def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
     o = path_opts(3, sppse, (0, 0, 2))
     ga, gb = synthetic_grid(), synthetic_grid((4, 8, 2))
     mass_reso, nrounds = [8, 2, 2, 2], 2
-    tbc = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
-    desc, keep = make_desc(tbc, ga, device="cpu")
-    by_ptr = {t.data_ptr(): t for t in keep}
+    tbc, desc, keep = cpu_desc(tb, ga)
     path = str(tmp_path / "tables.bin")
-    with open(path, "wb") as f:
-        f.write(np.int64(C.sizeof(desc)).tobytes())
-        f.write(bytes(desc))
-        recs = []
-        for fname, ftype in desc._fields_:
-            if ftype is C.c_void_p and getattr(desc, fname):
-                recs.append((getattr(type(desc), fname).offset, by_ptr[getattr(desc, fname)]))
-        f.write(np.int64(len(recs)).tobytes())
-        for off, t in recs:
-            raw = t.numpy().tobytes()
-            f.write(np.array([off, len(raw)], np.int64).tobytes())
-            f.write(raw)
-        f.write(bytes(o))
-        f.write(np.array(gb[0], np.int32).tobytes())
-        f.write(np.float32(gb[3]).tobytes())
-        f.write(gb[1].numpy().astype(np.float32).tobytes())
-        f.write(gb[2].numpy().astype(np.float32).tobytes())
-        f.write(np.array(mass_reso + [nrounds], np.int32).tobytes())
-        f.write(tan["sec_edge"].detach().cpu().numpy().astype(np.float32).tobytes())
-        f.write(adj.astype(np.float32).tobytes())
+    write_tables_file(path, desc, keep, o, np.array(gb[0], np.int32), np.float32(gb[3]), gb[1].numpy().astype(np.float32), gb[2].numpy().astype(np.float32),
+                      np.array(mass_reso + [nrounds], np.int32), tan["sec_edge"].detach().cpu().numpy().astype(np.float32), adj.astype(np.float32))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([exe, path], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-3000:])
