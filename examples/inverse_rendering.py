@@ -4,6 +4,7 @@
     python examples/inverse_rendering.py albedo       # recover a wall colour (material parameter)
     python examples/inverse_rendering.py translation  # move an occluder back (geometry: all three terms)
     python examples/inverse_rendering.py envmap       # recover the environment map's pixels under a metal bunny
+    python examples/inverse_rendering.py svbrdf       # recover albedo and roughness maps of a quad from three flash photographs (CollocatedIntegrator)
     python examples/inverse_rendering.py shape        # recover a displaced sphere's vertices, one by one, through psdr_cuda.LargeSteps
 
 Needs an MI355X (the render path has no CPU fallback)."""
@@ -89,6 +90,69 @@ def envmap():
          lambda: "mean |map - truth| %.4f" % float(np.abs(env.radiance.data.numpy() - truth).mean()))
 
 
+SVBRDF_XML = """<scene version="0.5.0">
+<sensor type="perspective"><float name="fov" value="13"/><string name="fovAxis" value="x"/>
+<transform name="toWorld"><lookAt origin="0, 125, 1000" target="0, 125, 0" up="0, 1, 0"/></transform>
+<sampler type="independent"><integer name="sampleCount" value="4"/></sampler>
+<film type="hdrfilm"><integer name="width" value="64"/><integer name="height" value="64"/><rfilter type="box"/></film></sensor>
+<bsdf id="m" type="microfacet"><rgb name="specularReflectance" value="0.08, 0.08, 0.08"/></bsdf>
+<shape type="obj"><string name="filename" value="./data/objects/cbox/floor_uv.obj"/>
+<transform name="toWorld"><translate z="-50"/><scale x="0.9" z="0.6"/><rotate angle="90" x="1"/><rotate angle="%g" y="1"/><translate y="125"/></transform>
+<boolean name="faceNormals" value="true"/><ref id="m"/></shape>
+</scene>"""
+
+
+def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0)):
+    """A quad with map_res x map_res kd and roughness maps (MicrofacetBSDF, F0 known) photographed with a flash at the camera under three tilts -- one quad
+    transformed three times, the maps shared.  The diffuse lobe is seen at every tilt, the specular lobe only near normal incidence, so the two maps separate by
+    angle.  Adam on both maps from a flat start; the flash's intensity brings the pixel values (1 / distance^2 = 1e-6) to order 0.1."""
+    rng = np.random.default_rng(3)
+    kd_true = rng.uniform(0.2, 0.8, (map_res * map_res, 3)).astype(np.float32)
+    r_true = rng.uniform(0.3, 0.6, map_res * map_res).astype(np.float32)
+    integ = psdr_cuda.CollocatedIntegrator(1e6)
+
+    def view(tilt, spp_, kd, rough):
+        sc = psdr_cuda.Scene()
+        sc.load_string(SVBRDF_XML % tilt, False)
+        sc.opts.width = sc.opts.height = res
+        sc.opts.spp, sc.opts.sppe, sc.opts.sppse, sc.opts.log_level = spp_, 0, 0, 0
+        b = sc.param_map["BSDF[id=m]"]
+        b.diffuse_reflectance.resolution = b.roughness.resolution = (map_res, map_res)
+        b.diffuse_reflectance.data, b.roughness.data = kd, rough
+        return sc
+    targets = []
+    for tilt in tilts:
+        ref = view(tilt, 256, Vector3fD(torch.as_tensor(kd_true, device="cuda")), FloatD(torch.as_tensor(r_true, device="cuda")))
+        ref.configure()
+        targets.append(integ.renderC(ref).torch().clone())
+    kd = Vector3fD(torch.full((map_res * map_res, 3), 0.5, device="cuda"))
+    rough = FloatD(torch.full((map_res * map_res,), 0.45, device="cuda"))
+    ek.set_requires_gradient(kd)
+    ek.set_requires_gradient(rough)
+    views = [view(tilt, spp, kd, rough) for tilt in tilts]
+    opt = torch.optim.Adam([kd.t, rough.t], lr=0.03)
+
+    def report():
+        return "mean texel error: kd %.4f, roughness %.4f" % (float(np.abs(kd.numpy() - kd_true).mean()), float(np.abs(rough.numpy().reshape(-1) - r_true).mean()))
+    print("  start     %s" % report())
+    t0 = time.perf_counter()
+    for it in range(steps):
+        opt.zero_grad()
+        total = 0.0
+        for sc, target in zip(views, targets):
+            sc.configure()
+            loss = ek.hmean(ek.hsum(ek.sqr(integ.renderD(sc) - Vector3fD._wrap(target))))
+            ek.backward(loss)
+            total += float(loss.t.item())
+        opt.step()
+        kd.t.data.clamp_(0.01, 0.99)
+        rough.t.data.clamp_(0.05, 1.0)
+        if it % 10 == 0 or it == steps - 1:
+            print("  step %3d  loss %.5f  %s" % (it, total, report()))
+    torch.cuda.synchronize()
+    print("  %.1f ms per step (three views)" % ((time.perf_counter() - t0) / steps * 1e3))
+
+
 def icosphere(level):
     """unit icosphere: (vertices [V, 3], faces [F, 3])"""
     t = (1.0 + 5.0 ** 0.5) / 2.0
@@ -144,4 +208,4 @@ def shape():
 
 
 if __name__ == "__main__":
-    {"albedo": albedo, "translation": translation, "envmap": envmap, "shape": shape}[sys.argv[1] if len(sys.argv) > 1 else "albedo"]()
+    {"albedo": albedo, "translation": translation, "envmap": envmap, "svbrdf": svbrdf, "shape": shape}[sys.argv[1] if len(sys.argv) > 1 else "albedo"]()

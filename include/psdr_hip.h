@@ -58,12 +58,21 @@ extern "C" {
 /* BSDF types (src/bsdf/diffuse.cpp, src/bsdf/roughconductor.cpp) */
 #define PSDR_BSDF_DIFFUSE        0
 #define PSDR_BSDF_ROUGHCONDUCTOR 1
+/* MicrofacetBSDF (build-defined, DESIGN.md section 14, csrc/psdr_colloc_microfacet.h): Lambertian diffuse + isotropic GGX specular with a Schlick
+   Fresnel term.  Evaluated by PSDR_INTEGRATOR_COLLOCATED only: every other integrator that evaluates a BSDF returns an error on a scene that
+   announces this type. */
+#define PSDR_BSDF_MICROFACET     2
 /* bsdf_rec parameter slots: slot s occupies words 1+3*s .. 3+3*s */
 #define PSDR_SLOT_REFLECTANCE 0 /* Diffuse::m_reflectance / RoughConductor::m_specular_reflectance (3 ch) */
 #define PSDR_SLOT_ALPHA_U     1 /* 1 ch */
 #define PSDR_SLOT_ALPHA_V     2 /* 1 ch */
 #define PSDR_SLOT_ETA         3 /* 3 ch */
 #define PSDR_SLOT_K           4 /* 3 ch */
+/* PSDR_BSDF_MICROFACET keeps the record's stride and reads three of its slots:
+     PSDR_SLOT_REFLECTANCE  diffuse_reflectance kd (3 ch)
+     PSDR_SLOT_ALPHA_U      roughness r (1 ch); the GGX width is alpha = r^2 in both directions
+     PSDR_SLOT_ETA          specular_reflectance F0 (3 ch)
+   PSDR_SLOT_ALPHA_V and PSDR_SLOT_K are unused and hold (offset, width, height) = (0, 1, 1). */
 
 /* cam[] layout (PerspectiveCamera, src/sensor/perspective.cpp:11-33), row-major 4x4 */
 #define PSDR_CAM_SAMPLE_TO_CAMERA  0
@@ -142,7 +151,9 @@ typedef struct psdr_scene_desc {
     /* Bit t set = a BSDF of type t (PSDR_BSDF_*) occurs in bsdf_rec; 0 = unknown (the library then keeps
        the code of every BSDF type in its kernels).  A host that knows its materials sets it so that, e.g.,
        an all-diffuse scene runs the kernel variant compiled without the GGX / conductor-Fresnel code.
-       Bits that are clear MUST be right: a cleared type is evaluated as diffuse. */
+       Bits that are clear MUST be right: a cleared type is evaluated as diffuse.
+       Bit PSDR_BSDF_MICROFACET (2) announces a MicrofacetBSDF record.  That type is never "unknown": with material_mask == 0 the caller
+       promises that no PSDR_BSDF_MICROFACET record is present. */
     uint32_t       material_mask;
     /* [E][2] global triangle ids of the one or two faces adjacent to every secondary edge (second = -1 on a
        boundary edge), or NULL.  Not in the reference's SecondaryEdgeInfo (edge.h:27-65): the two rays that

@@ -9,6 +9,7 @@
 // (tests/hostcheck/hostcheck_collocated.cpp) instantiate the functions below.
 #pragma once
 #include "psdr_reverse.h"
+#include "psdr_colloc_microfacet.h"
 
 namespace psdr {
 
@@ -20,7 +21,7 @@ PSDR_HD Vec3<M> li_collocated(const SceneView &sc, const TVT &tv, TraversalStack
     const int bsdf_id = Tab<TVT::flags>::mesh_bsdf(sc, its.mesh);
     if (bsdf_id < 0) return zero3<M>();          // the bounding mesh of an environment map has no BSDF
     const Bsdf<G, M> bsdf(sc, tv, bsdf_id);
-    const Vec3<M> f = bsdf.eval(sc, tv, its, its.wi, true);
+    const Vec3<M> f = colloc_bsdf_eval<TVT::has_rough>(sc, tv, bsdf, its, its.wi);          // MicrofacetBSDF by the record's type (psdr_colloc_microfacet.h)
     const Vec3<G> dv = its.p - ray.o;
     const G inv_d2 = 1.f / dot(dv, dv);
     return f * to_m<M>(inv_d2);
@@ -151,7 +152,7 @@ PSDR_HD Vec3f collocated_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, co
     const int bsdf_id = Tab<RealSink::flags>::mesh_bsdf(sc, its.mesh);
     if (bsdf_id < 0) return Vec3f(0.f);
     BsdfRev<Sink> brev(sc, bsdf_id);
-    const Vec3f f = brev.b.eval(sc, tv0, its, its.wi, true);
+    const Vec3f f = colloc_bsdf_eval<(Sink::flags & kSceneRough) != 0>(sc, tv0, brev.b, its, its.wi);
     const Vec3f dv = its.p - ray.o;
     const float inv_d2 = 1.f / dot(dv, dv);
     const Vec3f result = f * inv_d2;
@@ -159,7 +160,7 @@ PSDR_HD Vec3f collocated_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, co
     const Vec3f a{isfinite(result.x) ? adj.x : 0.f, isfinite(result.y) ? adj.y : 0.f, isfinite(result.z) ? adj.z : 0.f};
     VertexAdj va0; va0.clear();
     Vec3f a_wo(0.f);
-    brev.eval_vjp(sink, tv0, its, its.wi, a * inv_d2, va0.wi, a_wo, va0.u, va0.v);
+    colloc_bsdf_eval_vjp(sink, sc, tv0, brev, its, its.wi, a * inv_d2, va0.wi, a_wo, va0.u, va0.v);
     acc(va0.wi, a_wo);                                                   // wo = wi
     if (GEO) {
         // 1 / |p - o|^2, then the primary vertex: wi = to_local(-d), frame(sh_n(bu, bv)), uv(bu, bv), p = p0 + bu e1 + bv e2, (bu, bv, t) = MT(tri0, ray)

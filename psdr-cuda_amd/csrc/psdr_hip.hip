@@ -600,6 +600,13 @@ int check_counts(const psdr_scene_s *h, const psdr_render_opts *o) {
     if (o->sppse_begin < 0 || o->sppse_end > o->sppse || o->sppse_begin > o->sppse_end) return fail("Invalid sppse shard range");
     return 0;
 }
+// MicrofacetBSDF (PSDR_BSDF_MICROFACET) has an evaluation and its adjoint, no sample / pdf: the integrators that sample a BSDF refuse the scene before
+// any launch.  PSDR_INTEGRATOR_FIELD evaluates no BSDF (psdr_device.h Li returns the field before any material is read) and passes.
+int check_microfacet(const psdr_scene_s *h, const psdr_render_opts *o) {
+    if (h->has_microfacet && (o->integrator == PSDR_INTEGRATOR_DIRECT || o->integrator == PSDR_INTEGRATOR_PATH))
+        return fail("MicrofacetBSDF is evaluated by the CollocatedIntegrator only");
+    return 0;
+}
 
 // Strategy choice: a PURE FUNCTION of the scene and the options (round 3; it used to follow the survival ratio the previous PathTracer
 // call on the handle had measured, so the same call could run either strategy depending on the call history -- and the two agree only
@@ -1131,7 +1138,9 @@ int psdr_scene_set_tables(psdr_scene_t h, const psdr_scene_desc *desc) {
     if (!h->have_tables || std::memcmp(&h->desc, &d, sizeof(d)) != 0) { ++h->tables_gen; h->kept.valid = false; }
     h->desc = d;
     // material_mask = 0: unknown -> serve every BSDF type
-    h->has_rough = d.material_mask == 0 || (d.material_mask & (1u << PSDR_BSDF_ROUGHCONDUCTOR)) != 0;
+    // ... except MicrofacetBSDF, which only its own bit announces (psdr_hip.h); it lives in the GGX code of the collocated rough flag sets
+    h->has_microfacet = (d.material_mask & (1u << PSDR_BSDF_MICROFACET)) != 0;
+    h->has_rough = d.material_mask == 0 || (d.material_mask & (1u << PSDR_BSDF_ROUGHCONDUCTOR)) != 0 || h->has_microfacet;
     h->have_tables = true;
     h->pg_cmf = h->pg_pmf = nullptr; h->pg_sum = 0.f;          // segment B's guiding grid belongs to the tables it was built for (psdr_scene_set_path_guide)
     return 0;
@@ -1420,6 +1429,7 @@ int psdr_render_c(psdr_scene_t h, const psdr_render_opts *o, float *out_img, voi
     if (!h || !o || !out_img) return fail("psdr_render_c: null argument");
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (int rc = check_counts(h, o)) return rc;
+    if (int rc = check_microfacet(h, o)) return rc;
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
     if (o->integrator == PSDR_INTEGRATOR_PATH) h->last_path_depth = o->max_depth;
@@ -1434,6 +1444,7 @@ int psdr_render_d_fwd(psdr_scene_t h, const psdr_render_opts *o, int32_t K, cons
     if (!h || !o || !out_img || !out_dimg || !tangents) return fail("psdr_render_d_fwd: null argument");
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (int rc = check_counts(h, o)) return rc;
+    if (int rc = check_microfacet(h, o)) return rc;
     if (int rc = check_path_sedges(o)) return rc;
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
@@ -1448,6 +1459,7 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
     if (!h || !o || !adj_img || !grads) return fail("psdr_render_d_rev: null argument");
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (int rc = check_counts(h, o)) return rc;
+    if (int rc = check_microfacet(h, o)) return rc;
     if (int rc = check_path_sedges(o)) return rc;
     if (o->flags & PSDR_FLAG_LITERAL_FORMS) return fail("psdr_render_d_rev: PSDR_FLAG_LITERAL_FORMS is a forward-mode diagnostic (no literal-form adjoint)");
     if (o->integrator == PSDR_INTEGRATOR_PATH && o->max_depth > kMaxRevDepthDeep)
@@ -1463,6 +1475,7 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
 
 int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *o, const int32_t reso[4], int32_t nrounds, float *out_mass, void *stream) {
     if (!h || !o || !reso || !out_mass) return fail("psdr_guide_build: null argument");
+    if (int rc = check_microfacet(h, o)) return rc;
     if (nrounds <= 0) return fail("psdr_guide_build: nrounds must be positive");
     if (h->desc.num_sec_edges <= 0) return fail("psdr_guide_build: scene has no secondary edges");
     hipStream_t s = (hipStream_t) stream;
@@ -1479,6 +1492,7 @@ int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *o, const int32_t re
 
 int psdr_path_guide_build(psdr_scene_t h, const psdr_render_opts *o, int32_t segment, const int32_t reso[4], int32_t nrounds, float *out_mass, void *stream) {
     if (!h || !o || !reso || !out_mass) return fail("psdr_path_guide_build: null argument");
+    if (int rc = check_microfacet(h, o)) return rc;
     if (nrounds <= 0) return fail("psdr_path_guide_build: nrounds must be positive");
     if (o->integrator != PSDR_INTEGRATOR_PATH) return fail("psdr_path_guide_build: the integrator must be PSDR_INTEGRATOR_PATH");
     if (o->max_depth < 1) return fail("psdr_path_guide_build: max_depth must be at least 1");

@@ -305,6 +305,7 @@ struct psdr_scene_s {
     int32_t pg_reso[3] = {1, 1, 1};
     const float *pg_cmf = nullptr, *pg_pmf = nullptr;
     float pg_sum = 0.f;
+    bool has_microfacet = false;           // desc.material_mask announces a MicrofacetBSDF (PSDR_BSDF_MICROFACET): CollocatedIntegrator only
 };
 
 constexpr int kRayCounters = 64, kRayCounterStride = 16;     // d_counters: 64 counters, 128 bytes apart
@@ -338,6 +339,7 @@ inline int sink_bytes(const SinkLayout &L) { return L.pend_rows > 0 ? (L.pend_of
 // reserve the deferred-row block behind the cache and the private block: call when the layout is otherwise final
 inline void sink_reserve_pending(SinkLayout &L, int rows) { L.pend_rows = 0; L.pend_off = (sink_bytes_base(L) / 4 + 3) / 4 * 4; L.pend_rows = rows; }
 int check_counts(const psdr_scene_s *h, const psdr_render_opts *o);
+int check_microfacet(const psdr_scene_s *h, const psdr_render_opts *o);      // DirectIntegrator / PathTracer on a scene with a MicrofacetBSDF: an error
 int begin_call(psdr_scene_s *h, hipStream_t s);
 int primary_edge_order(psdr_scene_s *h, const LaunchCtx &cx, long long i0, long long n, const uint32_t **order, hipStream_t s);
 constexpr int kMaxRefits = 64;              // full SAH rebuild at least this often

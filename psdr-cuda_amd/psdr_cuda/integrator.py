@@ -17,7 +17,7 @@ import torch
 import enoki as ek
 from . import _abi
 from .core import Object, psdr_assert, Vector3fC, Vector3fD, HyperCubeDistribution3f
-from .scene import make_desc
+from .scene import make_desc, MicrofacetBSDF, MICROFACET_COLLOCATED_ONLY
 
 _AD_KEYS = _abi.TANGENT_FIELDS
 
@@ -324,8 +324,15 @@ class Integrator(Object):
         self._counters_src, self._counters_val = (lib, scene), None
         self._calls += 1
 
+    def _check_bsdfs(self, scene):
+        """MicrofacetBSDF is an evaluation without sample / pdf: the integrators that sample a BSDF refuse the scene before any native call (the
+        C ABI returns the same message)."""
+        if self._kind in (_abi.INTEGRATOR_DIRECT, _abi.INTEGRATOR_PATH) and any(isinstance(b, MicrofacetBSDF) for b in scene.m_bsdfs):
+            raise RuntimeError(MICROFACET_COLLOCATED_ONLY)
+
     # ---- public API (src/psdr.cpp:282-285) -------------------------------------------
     def renderC(self, scene, sensor_id=0):
+        self._check_bsdfs(scene)
         psdr_assert(scene.is_ready(), "Input scene must be configured!")
         psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")
         t0 = time.perf_counter()
@@ -341,6 +348,7 @@ class Integrator(Object):
         return Vector3fC._wrap(img.reshape(-1, 3))
 
     def renderD(self, scene, sensor_id=0):
+        self._check_bsdfs(scene)
         psdr_assert(scene.is_ready(), "Input scene must be configured!")
         psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")
         t0 = time.perf_counter()
@@ -393,6 +401,7 @@ class DirectIntegrator(Integrator):
         self.hide_emitters = False
 
     def preprocess_secondary_edges(self, scene, sensor_id, resolution, nrounds=1):
+        self._check_bsdfs(scene)
         psdr_assert(nrounds > 0)
         psdr_assert(scene.is_ready(), "Scene needs to be configured!")
         reso = [int(r) for r in np.asarray(resolution).reshape(-1)]
@@ -461,6 +470,7 @@ class PathTracer(Integrator):
             raise RuntimeError("preprocess_path_secondary_edges: PathTracer(secondary_edges=False) never evaluates the slots the grids would guide")
         if self.max_depth > _abi.MAX_PATH_SEDGE_DEPTH:
             raise RuntimeError("preprocess_path_secondary_edges: max_depth > %d is not supported for the secondary-edge term" % _abi.MAX_PATH_SEDGE_DEPTH)
+        self._check_bsdfs(scene)
         psdr_assert(nrounds > 0)
         psdr_assert(scene.is_ready(), "Scene needs to be configured!")
         psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")

@@ -101,6 +101,28 @@ class RoughConductor(BSDF):
 
 RoughConductorBSDF = RoughConductor
 
+MICROFACET_COLLOCATED_ONLY = "MicrofacetBSDF is evaluated by the CollocatedIntegrator only"
+
+
+class MicrofacetBSDF(BSDF):
+    """Lambertian diffuse + isotropic GGX specular with a Schlick Fresnel term (build-defined: DESIGN.md section 14, csrc/psdr_colloc_microfacet.h).
+    The argument order is the later reference versions': (specular_reflectance, diffuse_reflectance, roughness); the GGX width is roughness ** 2.
+    Defaults (also what the loader gives a missing child): F0 = 0.04, kd = 0.5, roughness = 0.5.  An evaluation without sample / pdf: the
+    CollocatedIntegrator renders it, DirectIntegrator and PathTracer raise."""
+    _type_name = "MicrofacetBSDF"
+
+    def __init__(self, specular_reflectance=None, diffuse_reflectance=None, roughness=None):
+        super().__init__()
+        self.specular_reflectance = specular_reflectance if isinstance(specular_reflectance, Bitmap3fD) else Bitmap3fD(
+            0.04 if specular_reflectance is None else specular_reflectance)
+        self.diffuse_reflectance = diffuse_reflectance if isinstance(diffuse_reflectance, Bitmap3fD) else Bitmap3fD(
+            0.5 if diffuse_reflectance is None else diffuse_reflectance)
+        self.roughness = roughness if isinstance(roughness, Bitmap1fD) else Bitmap1fD(0.5 if roughness is None else roughness)
+
+    def to_string(self):
+        return "MicrofacetBSDF[id=%s]" % self.id
+
+
 
 # ---------------------------------------------------------------------------- emitters
 class Emitter(Object):
@@ -1079,6 +1101,13 @@ class Scene(Object):
             alpha, eta, k = (_find_child(node, {n}) for n in ("alpha", "eta", "k"))
             _load_texture(alpha, b.alpha_u, base_dir); _load_texture(alpha, b.alpha_v, base_dir)
             _load_texture(eta, b.eta, base_dir); _load_texture(k, b.k, base_dir)
+        elif t == "microfacet":
+            b = MicrofacetBSDF()
+            for bitmap, names in ((b.diffuse_reflectance, {"diffuseReflectance", "diffuse_reflectance"}),
+                                  (b.specular_reflectance, {"specularReflectance", "specular_reflectance"}), (b.roughness, {"roughness"})):
+                child = _find_child(node, names, True)          # a missing child keeps the constructor's default
+                if child is not None:
+                    _load_texture(child, bitmap, base_dir)
         else:
             raise RuntimeError("Unsupported BSDF: " + str(t))
         b.id = bid
@@ -1293,6 +1322,8 @@ class Scene(Object):
             elif isinstance(b, RoughConductor):
                 r = ([_abi.BSDF_ROUGHCONDUCTOR] + put(b.specular_reflectance) + put(b.alpha_u) + put(b.alpha_v) +
                      put(b.eta) + put(b.k))
+            elif isinstance(b, MicrofacetBSDF):          # slots: kd, roughness, -, F0, - (include/psdr_hip.h)
+                r = ([_abi.BSDF_MICROFACET] + put(b.diffuse_reflectance) + put(b.roughness) + [0, 1, 1] + put(b.specular_reflectance) + [0, 1, 1])
             else:
                 raise RuntimeError("Unsupported BSDF: " + b.type_name())
             rec.append(r)
