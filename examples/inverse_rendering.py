@@ -5,6 +5,7 @@
     python examples/inverse_rendering.py translation  # move an occluder back (geometry: all three terms)
     python examples/inverse_rendering.py envmap       # recover the environment map's pixels under a metal bunny
     python examples/inverse_rendering.py svbrdf       # recover albedo and roughness maps of a quad from three flash photographs (CollocatedIntegrator)
+    python examples/inverse_rendering.py svbrdf --normals     # ... of a quad with a bumpy normal map: albedo, roughness and normals
     python examples/inverse_rendering.py shape        # recover a displaced sphere's vertices, one by one, through psdr_cuda.LargeSteps
 
 Needs an MI355X (the render path has no CPU fallback)."""
@@ -102,38 +103,62 @@ SVBRDF_XML = """<scene version="0.5.0">
 </scene>"""
 
 
-def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0)):
+def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False):
     """A quad with map_res x map_res kd and roughness maps (MicrofacetBSDF, F0 known) photographed with a flash at the camera under three tilts -- one quad
     transformed three times, the maps shared.  The diffuse lobe is seen at every tilt, the specular lobe only near normal incidence, so the two maps separate by
-    angle.  Adam on both maps from a flat start; the flash's intensity brings the pixel values (1 / distance^2 = 1e-6) to order 0.1."""
+    angle.  Adam on both maps from a flat start; the flash's intensity brings the pixel values (1 / distance^2 = 1e-6) to order 0.1.
+    normals (--normals): the target quad also carries a bumpy tangent-space normal map (leaning up to about 25 degrees) and the loop recovers kd, roughness AND
+    the normal map, started flat.  Tilts about one axis leave the sign of the normal's component along that axis open, so the third view tilts about x."""
     rng = np.random.default_rng(3)
     kd_true = rng.uniform(0.2, 0.8, (map_res * map_res, 3)).astype(np.float32)
     r_true = rng.uniform(0.3, 0.6, map_res * map_res).astype(np.float32)
     integ = psdr_cuda.CollocatedIntegrator(1e6)
+    if normals:
+        tilts = ((35.0, 0.0), (-35.0, 0.0), (0.0, 35.0))          # (about y, about x)
+        v_true = np.concatenate([rng.uniform(-0.35, 0.35, (map_res * map_res, 2)), np.ones((map_res * map_res, 1))], axis=1)
+        n_true = ((v_true + 1.0) / 2.0).astype(np.float32)          # the image encoding: texel = (v + 1) / 2
 
-    def view(tilt, spp_, kd, rough):
+    def view(tilt, spp_, kd, rough, nm=None):
         sc = psdr_cuda.Scene()
-        sc.load_string(SVBRDF_XML % tilt, False)
+        if normals:
+            sc.load_string((SVBRDF_XML % tilt[0]).replace('y="1"/><translate', 'y="1"/><rotate angle="%g" x="1"/><translate' % tilt[1]), False)
+        else:
+            sc.load_string(SVBRDF_XML % tilt, False)
         sc.opts.width = sc.opts.height = res
         sc.opts.spp, sc.opts.sppe, sc.opts.sppse, sc.opts.log_level = spp_, 0, 0, 0
         b = sc.param_map["BSDF[id=m]"]
         b.diffuse_reflectance.resolution = b.roughness.resolution = (map_res, map_res)
         b.diffuse_reflectance.data, b.roughness.data = kd, rough
+        if nm is not None:
+            b.normal_map = psdr_cuda.Bitmap3fD(map_res, map_res, nm)
         return sc
     targets = []
     for tilt in tilts:
-        ref = view(tilt, 256, Vector3fD(torch.as_tensor(kd_true, device="cuda")), FloatD(torch.as_tensor(r_true, device="cuda")))
+        ref = view(tilt, 256, Vector3fD(torch.as_tensor(kd_true, device="cuda")), FloatD(torch.as_tensor(r_true, device="cuda")),
+                   Vector3fD(torch.as_tensor(n_true, device="cuda")) if normals else None)
         ref.configure()
         targets.append(integ.renderC(ref).torch().clone())
     kd = Vector3fD(torch.full((map_res * map_res, 3), 0.5, device="cuda"))
     rough = FloatD(torch.full((map_res * map_res,), 0.45, device="cuda"))
     ek.set_requires_gradient(kd)
     ek.set_requires_gradient(rough)
-    views = [view(tilt, spp, kd, rough) for tilt in tilts]
-    opt = torch.optim.Adam([kd.t, rough.t], lr=0.03)
+    params = [kd.t, rough.t]
+    nm = None
+    if normals:
+        nm = Vector3fD(torch.tensor([[0.5, 0.5, 1.0]], device="cuda").repeat(map_res * map_res, 1))
+        ek.set_requires_gradient(nm)
+        params.append(nm.t)
+    views = [view(tilt, spp, kd, rough, nm) for tilt in tilts]
+    opt = torch.optim.Adam(params, lr=0.03)
+
+    def angle():
+        a, b = 2.0 * nm.numpy().astype(np.float64) - 1.0, 2.0 * n_true.astype(np.float64) - 1.0
+        a, b = a / np.linalg.norm(a, axis=1, keepdims=True), b / np.linalg.norm(b, axis=1, keepdims=True)
+        return float(np.degrees(np.arccos(np.clip((a * b).sum(1), -1.0, 1.0))).mean())
 
     def report():
-        return "mean texel error: kd %.4f, roughness %.4f" % (float(np.abs(kd.numpy() - kd_true).mean()), float(np.abs(rough.numpy().reshape(-1) - r_true).mean()))
+        return "mean texel error: kd %.4f, roughness %.4f%s" % (float(np.abs(kd.numpy() - kd_true).mean()), float(np.abs(rough.numpy().reshape(-1) - r_true).mean()),
+                                                               ", mean angular error of the normals %.2f degrees" % angle() if normals else "")
     print("  start     %s" % report())
     t0 = time.perf_counter()
     for it in range(steps):
@@ -147,6 +172,8 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0)):
         opt.step()
         kd.t.data.clamp_(0.01, 0.99)
         rough.t.data.clamp_(0.05, 1.0)
+        if normals:
+            nm.t.data.clamp_(0.0, 1.0)
         if it % 10 == 0 or it == steps - 1:
             print("  step %3d  loss %.5f  %s" % (it, total, report()))
     torch.cuda.synchronize()
@@ -208,4 +235,8 @@ def shape():
 
 
 if __name__ == "__main__":
-    {"albedo": albedo, "translation": translation, "envmap": envmap, "svbrdf": svbrdf, "shape": shape}[sys.argv[1] if len(sys.argv) > 1 else "albedo"]()
+    which = sys.argv[1] if len(sys.argv) > 1 else "albedo"
+    if which == "svbrdf" and "--normals" in sys.argv[2:]:
+        svbrdf(normals=True)
+    else:
+        {"albedo": albedo, "translation": translation, "envmap": envmap, "svbrdf": svbrdf, "shape": shape}[which]()

@@ -62,6 +62,12 @@ extern "C" {
    Fresnel term.  Evaluated by PSDR_INTEGRATOR_COLLOCATED only: every other integrator that evaluates a BSDF returns an error on a scene that
    announces this type. */
 #define PSDR_BSDF_MICROFACET     2
+/* MicrofacetBSDF with a tangent-space normal map (build-defined): the record of PSDR_BSDF_MICROFACET plus the map's
+   (offset, width, height) in PSDR_SLOT_K -- 3 channels, image encoding: texel c decodes to v = 2c - 1, (0.5, 0.5, 1) is "no perturbation".  The lobes
+   are evaluated about n' = normalize(s' v.x + t' v.y + n v.z): n the shading normal, s' the direction of increasing u on the triangle (from its three
+   tri_uv rows) made orthogonal to n, t' = n x s'.  Needs tri_uv: the render entry points return an error for a scene that announces the type and has
+   none.  Served like PSDR_BSDF_MICROFACET: PSDR_INTEGRATOR_COLLOCATED only. */
+#define PSDR_BSDF_MICROFACET_NORMAL 3
 /* bsdf_rec parameter slots: slot s occupies words 1+3*s .. 3+3*s */
 #define PSDR_SLOT_REFLECTANCE 0 /* Diffuse::m_reflectance / RoughConductor::m_specular_reflectance (3 ch) */
 #define PSDR_SLOT_ALPHA_U     1 /* 1 ch */
@@ -72,7 +78,9 @@ extern "C" {
      PSDR_SLOT_REFLECTANCE  diffuse_reflectance kd (3 ch)
      PSDR_SLOT_ALPHA_U      roughness r (1 ch); the GGX width is alpha = r^2 in both directions
      PSDR_SLOT_ETA          specular_reflectance F0 (3 ch)
-   PSDR_SLOT_ALPHA_V and PSDR_SLOT_K are unused and hold (offset, width, height) = (0, 1, 1). */
+   PSDR_SLOT_ALPHA_V and PSDR_SLOT_K are unused and hold (offset, width, height) = (0, 1, 1).
+   PSDR_BSDF_MICROFACET_NORMAL reads the same three and
+     PSDR_SLOT_K            normal_map (3 ch) */
 
 /* cam[] layout (PerspectiveCamera, src/sensor/perspective.cpp:11-33), row-major 4x4 */
 #define PSDR_CAM_SAMPLE_TO_CAMERA  0
@@ -153,7 +161,8 @@ typedef struct psdr_scene_desc {
        an all-diffuse scene runs the kernel variant compiled without the GGX / conductor-Fresnel code.
        Bits that are clear MUST be right: a cleared type is evaluated as diffuse.
        Bit PSDR_BSDF_MICROFACET (2) announces a MicrofacetBSDF record.  That type is never "unknown": with material_mask == 0 the caller
-       promises that no PSDR_BSDF_MICROFACET record is present. */
+       promises that no PSDR_BSDF_MICROFACET record is present.  Bit PSDR_BSDF_MICROFACET_NORMAL (3) announces a normal-mapped one in the same way
+       (never "unknown" either) and selects the same kernels as bit 2. */
     uint32_t       material_mask;
     /* [E][2] global triangle ids of the one or two faces adjacent to every secondary edge (second = -1 on a
        boundary edge), or NULL.  Not in the reference's SecondaryEdgeInfo (edge.h:27-65): the two rays that

@@ -8,20 +8,21 @@
 // the diffuse lobe.
 // The model is an evaluation and its adjoint, no sample / pdf: the CollocatedIntegrator (psdr_collocated.h) evaluates f at ONE direction pair, wo = wi (there
 // h = wi and F = F0), and is the only integrator that serves the type.  Both functions take a general wo all the same.
+// PSDR_BSDF_MICROFACET_NORMAL is the same record plus a tangent-space normal map in PSDR_SLOT_K: the lobes are evaluated about a
+// normal n' turned away from the shading normal in a frame whose tangent follows the texture's u axis (normal_map_frame below).
 // Compiled only into the flag sets that carry the GGX code (kSceneRough); the Lambertian ones keep their text.
 #pragma once
 #include "psdr_reverse.h"
 
 namespace psdr {
 
-// G: geometry type of the hit and the directions, M: material / result type -- plain floats, Dual<1> and Dual<3> go through this one copy
+// G: geometry type of the hit and the directions, M: material / result type -- plain floats, Dual<1> and Dual<3> go through this one copy.  The two lobes for
+// local directions that passed the side test (its: the texture coordinates of the lookups)
 template <class G, class M, class TVT>
-PSDR_HD Vec3<M> microfacet_eval(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its, const Vec3<G> &wo, bool active) {
-    if (!(active && val(its.wi.z) > 0.f && val(wo.z) > 0.f)) return zero3<M>();
-    const Vec3<M> diffuse = b.tex3(sc, tv, PSDR_SLOT_REFLECTANCE, its) * (wo.z * kInvPi);
+PSDR_HD Vec3<M> microfacet_lobes(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its, const Vec3<M> &wi_m, const Vec3<M> &wo_m) {
+    const Vec3<M> diffuse = b.tex3(sc, tv, PSDR_SLOT_REFLECTANCE, its) * (wo_m.z * kInvPi);
     const M alpha = sqr(b.tex1(sc, tv, PSDR_SLOT_ALPHA_U, its));
     const GGX<M> g{alpha, alpha};
-    const Vec3<M> wi_m = to_m3<M>(its.wi), wo_m = to_m3<M>(wo);
     const Vec3<M> H = normalize(wo_m + wi_m);
     const M D = g.eval(H);
     if (val(D) == 0.f) return diffuse;
@@ -31,14 +32,18 @@ PSDR_HD Vec3<M> microfacet_eval(const SceneView &sc, const TVT &tv, const Bsdf<G
     const M w = sqr(sqr(t)) * t;
     return {diffuse.x + (F0.x + (1.f - F0.x) * w) * res, diffuse.y + (F0.y + (1.f - F0.y) * w) * res, diffuse.z + (F0.z + (1.f - F0.z) * w) * res};
 }
+template <class G, class M, class TVT>
+PSDR_HD Vec3<M> microfacet_eval(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its, const Vec3<G> &wo, bool active) {
+    if (!(active && val(its.wi.z) > 0.f && val(wo.z) > 0.f)) return zero3<M>();
+    return microfacet_lobes<G, M>(sc, tv, b, its, to_m3<M>(its.wi), to_m3<M>(wo));
+}
 
-// Adjoint of value = microfacet_eval(its, wo), with BsdfRev::eval_vjp's signature: af (RGB) -> awi, awo, the texels of the three maps (through the sink), a_uv.
+// Adjoint of value = microfacet_lobes(its, wi, wo): af (RGB) -> awi, awo, the texels of the three maps (through the sink), a_uv.
 // The geometric part D G1 G1 / (4 wi.z) and the Fresnel cosine go through ggx_geo_vjp (psdr_reverse.h), the rough conductor's own.  An adjoint that is not
 // finite (alpha at the edge of fp32) is dropped like the sample's value is (zero_nonfinite).
 template <class Sink, class TVT>
-PSDR_HD void microfacet_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0, const Bsdf<float, float> &b, const Its<float> &its, const Vec3f &wo,
-                                 const Vec3f &af, Vec3f &awi, Vec3f &awo, float &auvx, float &auvy) {
-    if (!(its.wi.z > 0.f && wo.z > 0.f)) return;
+PSDR_HD void microfacet_lobes_vjp(Sink &sink, const SceneView &sc, const TVT &tv0, const Bsdf<float, float> &b, const Its<float> &its, const Vec3f &wi, const Vec3f &wo,
+                                  const Vec3f &af, Vec3f &awi, Vec3f &awo, float &auvx, float &auvy) {
     {   // kd / pi * wo.z
         const Vec3f kd = b.tex3(sc, tv0, PSDR_SLOT_REFLECTANCE, its);
         const float c = wo.z * kInvPi;
@@ -47,7 +52,7 @@ PSDR_HD void microfacet_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0
         awo.z += dot(af, kd) * kInvPi;
     }
     const float r = b.tex1(sc, tv0, PSDR_SLOT_ALPHA_U, its), alpha = r * r;
-    const GgxAdj v0 = ggx_geo_vjp<true>(its.wi, wo, alpha, alpha, 0.f, 0.f);          // value pass: geo = D G1 G1 / (4 wi.z), c = wi.h
+    const GgxAdj v0 = ggx_geo_vjp<true>(wi, wo, alpha, alpha, 0.f, 0.f);          // value pass: geo = D G1 G1 / (4 wi.z), c = wi.h
     if (v0.zero || !isfinite(v0.geo)) return;
     const Vec3f F0 = b.tex3(sc, tv0, PSDR_SLOT_ETA, its);
     const float t = 1.f - v0.c, t4 = sqr(sqr(t)), w = t4 * t;
@@ -60,25 +65,131 @@ PSDR_HD void microfacet_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0
         a_geo += afp[ch] * (f0[ch] + (1.f - f0[ch]) * w);
         a_c += afp[ch] * v0.geo * (1.f - f0[ch]) * (-5.f * t4);
     }
-    const GgxAdj ga = ggx_geo_vjp<true>(its.wi, wo, alpha, alpha, a_geo, a_c);
+    const GgxAdj ga = ggx_geo_vjp<true>(wi, wo, alpha, alpha, a_geo, a_c);
     acc_finite(awi, ga.wi); acc_finite(awo, ga.wo);
     const float a_r = finite_or_zero((ga.au + ga.av) * (2.f * r));          // alpha_u = alpha_v = r^2
     bitmap_vjp<Sink, 1>(sink, sc, b.slot(PSDR_SLOT_ALPHA_U), its.uvx, its.uvy, &a_r, auvx, auvy);
     bitmap_vjp<Sink, 3>(sink, sc, b.slot(PSDR_SLOT_ETA), its.uvx, its.uvy, a_f0, auvx, auvy);
+}
+// ... with BsdfRev::eval_vjp's signature
+template <class Sink, class TVT>
+PSDR_HD void microfacet_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0, const Bsdf<float, float> &b, const Its<float> &its, const Vec3f &wo,
+                                 const Vec3f &af, Vec3f &awi, Vec3f &awo, float &auvx, float &auvy) {
+    if (!(its.wi.z > 0.f && wo.z > 0.f)) return;
+    microfacet_lobes_vjp(sink, sc, tv0, b, its, its.wi, wo, af, awi, awo, auvx, auvy);
+}
+
+// ------------------------------------------------------------------ tangent-space normal map (PSDR_BSDF_MICROFACET_NORMAL)
+// The perturbed normal n' of a hit and the intermediate values its adjoint reads:
+//     v = 2 c - 1 (c: the map's texel at the hit's uv),   dp_du = e1 c1 + e2 c2,  c1 = dv2 / det,  c2 = -dv1 / det  (the triangle's three UVs),
+//     p = dp_du - n (n . dp_du),  s = normalize(p),  t = n x s,  m = s v.x + t v.y + n v.z,  n' = normalize(m)
+// zero: |v|^2 <= 1e-12, the BSDF value is zero; flat: no UV-aligned tangent exists (det == 0, |p|^2 <= 1e-20, or a scene without texture coordinates), n' = n.
+template <class M> struct NormalMap { Vec3<M> n, v, dp, p, s, t, m, n1; M ndp; float c1, c2; bool zero, flat; };
+template <class G, class M, class TVT>
+PSDR_HD NormalMap<M> normal_map_frame(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its) {
+    NormalMap<M> r;
+    const Vec3<M> c = b.tex3(sc, tv, PSDR_SLOT_K, its);
+    r.v = {2.f * c.x - 1.f, 2.f * c.y - 1.f, 2.f * c.z - 1.f};
+    r.n = r.n1 = to_m3<M>(its.sh.n);
+    r.zero = !(val(dot(r.v, r.v)) > 1e-12f);
+    r.flat = true;
+    if (r.zero || sc.d.tri_uv == nullptr) return r;
+    const float *q = Tab<TVT::flags>::tri_uv(sc, its.tri);
+    const float du1 = q[2] - q[0], dv1 = q[3] - q[1], du2 = q[4] - q[0], dv2 = q[5] - q[1], det = du1 * dv2 - du2 * dv1;
+    if (det == 0.f) return r;
+    const TriRow<G> T = load_tri<G>(sc, tv, its.tri);
+    r.c1 = dv2 / det; r.c2 = -dv1 / det;
+    r.dp = to_m3<M>(T.e1) * r.c1 + to_m3<M>(T.e2) * r.c2;
+    r.ndp = dot(r.n, r.dp);
+    r.p = r.dp - r.n * r.ndp;
+    if (!(val(dot(r.p, r.p)) > 1e-20f)) return r;
+    r.flat = false;
+    r.s = normalize(r.p);
+    r.t = cross(r.n, r.s);
+    r.m = r.s * r.v.x + r.t * r.v.y + r.n * r.v.z;
+    r.n1 = normalize(r.m);
+    return r;
+}
+
+// value = microfacet_lobes(wi', wo') with wi' = Frame(n').to_local(world wi), wo' likewise, where wi.z > 0, wo.z > 0 (the unperturbed side test stays) and
+// wi'.z > 0, wo'.z > 0; zero otherwise.  Frame(n') is the project's constructor: the lobes are isotropic, so how the frame is completed around n' does not
+// change the value (it depends on wi'.z, wo'.z and wi'.wo' alone).
+template <class G, class M, class TVT>
+PSDR_HD bool normal_map_directions(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its, const Vec3<G> &wo, Vec3<M> &wi1, Vec3<M> &wo1) {
+    const NormalMap<M> nm = normal_map_frame<G, M>(sc, tv, b, its);
+    if (nm.zero) return false;
+    const Frame<M> f1(nm.n1);
+    wi1 = f1.to_local(to_m3<M>(its.sh.to_world(its.wi))); wo1 = f1.to_local(to_m3<M>(its.sh.to_world(wo)));
+    return val(wi1.z) > 0.f && val(wo1.z) > 0.f;
+}
+// one body for both record types, so that an instance holds ONE copy of the lobes
+template <class G, class M, class TVT>
+PSDR_HD Vec3<M> microfacet_any_eval(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its, const Vec3<G> &wo, bool normal_map) {
+    if (!(val(its.wi.z) > 0.f && val(wo.z) > 0.f)) return zero3<M>();
+    Vec3<M> wi_m = to_m3<M>(its.wi), wo_m = to_m3<M>(wo);
+    if (normal_map) { if (!normal_map_directions<G, M>(sc, tv, b, its, wo, wi_m, wo_m)) return zero3<M>(); }
+    return microfacet_lobes<G, M>(sc, tv, b, its, wi_m, wo_m);
+}
+
+// What the adjoint of a normal-mapped record adds to BsdfRev::eval_vjp's outputs: the adjoints of the hit's shading frame (the value reads the WORLD
+// directions sh.to_world(wi), sh.to_world(wo) and the shading normal) and of the triangle's two edges (through dp_du).  on: the record was of that type --
+// collocated_sample_reverse adds nothing otherwise, so every other record keeps its arithmetic.
+struct NormalMapAdj {
+    Vec3f s, t, n, e1, e2; bool on;
+    PSDR_HD void clear() { s = t = n = e1 = e2 = Vec3f(0.f); on = false; }
+};
+// Adjoint of value = microfacet_normal_eval(its, wo): af -> awi, awo, the texels of the four maps, a_uv, x.  The normal texels receive 2 a_v (v = 2 c - 1); nothing where
+// the value is defined as zero, nothing to the normal texels where n' = n.
+template <class Sink, class TVT>
+PSDR_HD void microfacet_normal_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0, const Bsdf<float, float> &b, const Its<float> &its, const Vec3f &wo,
+                                        const Vec3f &af, Vec3f &awi, Vec3f &awo, NormalMapAdj &x, float &auvx, float &auvy) {
+    x.on = true;
+    if (!(its.wi.z > 0.f && wo.z > 0.f)) return;
+    const NormalMap<float> nm = normal_map_frame<float, float>(sc, tv0, b, its);
+    if (nm.zero) return;
+    const Frame<float> f1(nm.n1);
+    const Vec3f Wi = its.sh.to_world(its.wi), Wo = its.sh.to_world(wo);
+    const Vec3f wi1 = f1.to_local(Wi), wo1 = f1.to_local(Wo);
+    if (!(wi1.z > 0.f && wo1.z > 0.f)) return;
+    Vec3f awi1(0.f), awo1(0.f);
+    microfacet_lobes_vjp(sink, sc, tv0, b, its, wi1, wo1, af, awi1, awo1, auvx, auvy);
+    // wi' = (Wi . s1, Wi . t1, Wi . n'), (s1, t1, n') = Frame(n')
+    // ... and Wi = sh.s wi.x + sh.t wi.y + sh.n wi.z, as forward mode evaluates it (Wo likewise)
+    const Vec3f aWi = f1.to_world(awi1), aWo = f1.to_world(awo1);
+    acc_finite(awi, its.sh.to_local(aWi)); acc_finite(awo, its.sh.to_local(aWo));
+    acc_finite(x.s, aWi * its.wi.x + aWo * wo.x); acc_finite(x.t, aWi * its.wi.y + aWo * wo.y); acc_finite(x.n, aWi * its.wi.z + aWo * wo.z);
+    const Vec3f an1 = Wi * awi1.z + Wo * awo1.z + frame_vjp(nm.n1, Wi * awi1.x + Wo * awo1.x, Wi * awi1.y + Wo * awo1.y);
+    if (nm.flat) { acc_finite(x.n, an1); return; }
+    const Vec3f am = normalize_vjp(nm.m, nm.n1, an1);
+    const float a_c[3] = {finite_or_zero(2.f * dot(am, nm.s)), finite_or_zero(2.f * dot(am, nm.t)), finite_or_zero(2.f * dot(am, nm.n))};
+    bitmap_vjp<Sink, 3>(sink, sc, b.slot(PSDR_SLOT_K), its.uvx, its.uvy, a_c, auvx, auvy);
+    // m = s v.x + t v.y + n v.z,  t = n x s,  s = normalize(p),  p = dp - n (n . dp),  dp = e1 c1 + e2 c2
+    const Vec3f a_t = am * nm.v.y;
+    const Vec3f a_s = am * nm.v.x + cross(a_t, nm.n);
+    const Vec3f a_p = normalize_vjp(nm.p, nm.s, a_s);
+    const float nap = dot(nm.n, a_p);
+    const Vec3f a_dp = a_p - nm.n * nap;
+    acc_finite(x.n, am * nm.v.z + cross(nm.s, a_t) - a_p * nm.ndp - nm.dp * nap);
+    acc_finite(x.e1, a_dp * nm.c1); acc_finite(x.e2, a_dp * nm.c2);
 }
 
 // The collocated estimator's BSDF value and its adjoint: MicrofacetBSDF by the record's type where the instance carries the GGX code (ROUGH), Bsdf::eval /
 // BsdfRev::eval_vjp for every other record and in every other instance
 template <bool ROUGH, class G, class M, class TVT>
 PSDR_HD Vec3<M> colloc_bsdf_eval(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its, const Vec3<G> &wo) {
-    if constexpr (ROUGH) { if (b.type() == PSDR_BSDF_MICROFACET) return microfacet_eval<G, M>(sc, tv, b, its, wo, true); }
+    if constexpr (ROUGH) {
+        const int type = b.type();
+        if (type == PSDR_BSDF_MICROFACET || type == PSDR_BSDF_MICROFACET_NORMAL) return microfacet_any_eval<G, M>(sc, tv, b, its, wo, type == PSDR_BSDF_MICROFACET_NORMAL);
+    }
     return b.eval(sc, tv, its, wo, true);
 }
+// x: what a normal-mapped record adds (NormalMapAdj); untouched by every other record
 template <class Sink, class TVT>
 PSDR_HD void colloc_bsdf_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0, const BsdfRev<Sink> &brev, const Its<float> &its, const Vec3f &wo, const Vec3f &af,
-                                  Vec3f &awi, Vec3f &awo, float &auvx, float &auvy) {
+                                  Vec3f &awi, Vec3f &awo, float &auvx, float &auvy, NormalMapAdj &x) {
     if constexpr ((Sink::flags & kSceneRough) != 0) {
         if (brev.b.type() == PSDR_BSDF_MICROFACET) { microfacet_eval_vjp(sink, sc, tv0, brev.b, its, wo, af, awi, awo, auvx, auvy); return; }
+        if (brev.b.type() == PSDR_BSDF_MICROFACET_NORMAL) { microfacet_normal_eval_vjp(sink, sc, tv0, brev.b, its, wo, af, awi, awo, x, auvx, auvy); return; }
     }
     brev.eval_vjp(sink, tv0, its, wo, af, awi, awo, auvx, auvy);
 }

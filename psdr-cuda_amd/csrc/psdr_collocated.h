@@ -160,8 +160,10 @@ PSDR_HD Vec3f collocated_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, co
     const Vec3f a{isfinite(result.x) ? adj.x : 0.f, isfinite(result.y) ? adj.y : 0.f, isfinite(result.z) ? adj.z : 0.f};
     VertexAdj va0; va0.clear();
     Vec3f a_wo(0.f);
-    colloc_bsdf_eval_vjp(sink, sc, tv0, brev, its, its.wi, a * inv_d2, va0.wi, a_wo, va0.u, va0.v);
+    NormalMapAdj nx; nx.clear();                                         // a normal-mapped MicrofacetBSDF: adjoints of the shading frame and of e1, e2 (dp_du)
+    colloc_bsdf_eval_vjp(sink, sc, tv0, brev, its, its.wi, a * inv_d2, va0.wi, a_wo, va0.u, va0.v, nx);
     acc(va0.wi, a_wo);                                                   // wo = wi
+    constexpr bool kNormalMaps = (Sink::flags & kSceneRough) != 0;       // (the type is compiled into the rough flag sets only)
     if (GEO) {
         // 1 / |p - o|^2, then the primary vertex: wi = to_local(-d), frame(sh_n(bu, bv)), uv(bu, bv), p = p0 + bu e1 + bv e2, (bu, bv, t) = MT(tri0, ray)
         const float a_d2 = -dot(a, zero_nonfinite(f)) * inv_d2 * inv_d2;
@@ -170,12 +172,19 @@ PSDR_HD Vec3f collocated_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, co
         const Vec3f dcam = camera_space_dir(sc, sx, sy);
         const Vec3f a_d = -(its.sh.s * va0.wi.x + its.sh.t * va0.wi.y + its.sh.n * va0.wi.z);
         acc(va0.s, ray.d * (-va0.wi.x)); acc(va0.t, ray.d * (-va0.wi.y)); acc(va0.n, ray.d * (-va0.wi.z));
+        if constexpr (kNormalMaps) { if (nx.on) { acc(va0.s, nx.s); acc(va0.t, nx.t); acc(va0.n, nx.n); } }
         const Vec3f a_shn = va0.n + frame_vjp(sn0.n, va0.s, va0.t);
         float abu = dot(va0.p, T0.e1), abv = dot(va0.p, T0.e2);
         shading_normal_vjp(sink, h0.tri, T0, sn0, bu, bv, a_shn, abu, abv);
         if (q) { abu += va0.u * (q[2] - q[0]) + va0.v * (q[3] - q[1]); abv += va0.u * (q[4] - q[0]) + va0.v * (q[5] - q[1]); }
         const MtAdj ma = mt_vjp(T0.p0, T0.e1, T0.e2, ray, abu, abv, 0.f);
-        scatter_vec(sink, h0.tri, 0, ma.p0 + va0.p); scatter_vec(sink, h0.tri, 3, ma.e1 + va0.p * bu); scatter_vec(sink, h0.tri, 6, ma.e2 + va0.p * bv);
+        if constexpr (kNormalMaps) {          // ... and dp_du of the tangent frame
+            Vec3f a_e1 = ma.e1 + va0.p * bu, a_e2 = ma.e2 + va0.p * bv;
+            if (nx.on) { acc(a_e1, nx.e1); acc(a_e2, nx.e2); }
+            scatter_vec(sink, h0.tri, 0, ma.p0 + va0.p); scatter_vec(sink, h0.tri, 3, a_e1); scatter_vec(sink, h0.tri, 6, a_e2);
+        } else {
+            scatter_vec(sink, h0.tri, 0, ma.p0 + va0.p); scatter_vec(sink, h0.tri, 3, ma.e1 + va0.p * bu); scatter_vec(sink, h0.tri, 6, ma.e2 + va0.p * bv);
+        }
         camera_ray_vjp(sink, sc, dcam, ma.o - a_dv, a_d + ma.d);
     }
     return zero_nonfinite(result);

@@ -17,7 +17,7 @@ import torch
 import enoki as ek
 from . import _abi
 from .core import Object, psdr_assert, Vector3fC, Vector3fD, HyperCubeDistribution3f
-from .scene import make_desc, MicrofacetBSDF, MICROFACET_COLLOCATED_ONLY
+from .scene import make_desc, MicrofacetBSDF, MICROFACET_COLLOCATED_ONLY, NORMAL_MAP_NEEDS_UV
 
 _AD_KEYS = _abi.TANGENT_FIELDS
 
@@ -329,6 +329,9 @@ class Integrator(Object):
         C ABI returns the same message)."""
         if self._kind in (_abi.INTEGRATOR_DIRECT, _abi.INTEGRATOR_PATH) and any(isinstance(b, MicrofacetBSDF) for b in scene.m_bsdfs):
             raise RuntimeError(MICROFACET_COLLOCATED_ONLY)
+        # a normal map's tangent frame follows the texture coordinates: a mesh without them has no defined value (the C ABI refuses a scene without the table)
+        if any(isinstance(m.bsdf, MicrofacetBSDF) and m.bsdf.normal_map is not None and not m.m_has_uv for m in scene.m_meshes):
+            raise RuntimeError(NORMAL_MAP_NEEDS_UV)
 
     # ---- public API (src/psdr.cpp:282-285) -------------------------------------------
     def renderC(self, scene, sensor_id=0):
@@ -593,6 +596,7 @@ class CollocatedIntegrator(Integrator):
         return Vector3fC._wrap(img.t * self.m_intensity.t.detach().reshape(1, 3).to(img.t.device))
 
     def renderD(self, scene, sensor_id=0):
+        self._check_bsdfs(scene)          # (a normal map on a mesh without texture coordinates)
         psdr_assert(scene.is_ready(), "Input scene must be configured!")
         psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")
         t0 = time.perf_counter()

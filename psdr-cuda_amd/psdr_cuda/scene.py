@@ -102,22 +102,27 @@ class RoughConductor(BSDF):
 RoughConductorBSDF = RoughConductor
 
 MICROFACET_COLLOCATED_ONLY = "MicrofacetBSDF is evaluated by the CollocatedIntegrator only"
+NORMAL_MAP_NEEDS_UV = "a normal map needs texture coordinates"
 
 
 class MicrofacetBSDF(BSDF):
     """Lambertian diffuse + isotropic GGX specular with a Schlick Fresnel term (build-defined: DESIGN.md section 14, csrc/psdr_colloc_microfacet.h).
     The argument order is the later reference versions': (specular_reflectance, diffuse_reflectance, roughness); the GGX width is roughness ** 2.
     Defaults (also what the loader gives a missing child): F0 = 0.04, kd = 0.5, roughness = 0.5.  An evaluation without sample / pdf: the
-    CollocatedIntegrator renders it, DirectIntegrator and PathTracer raise."""
+    CollocatedIntegrator renders it, DirectIntegrator and PathTracer raise.
+    normal_map: a tangent-space normal map in the image encoding -- texel c decodes to 2c - 1, (0.5, 0.5, 1) is "no perturbation" -- in
+    the frame (direction of increasing u made orthogonal to the shading normal, n x that, the shading normal); None: no map, the record of section 14.  A
+    Bitmap3fD is kept as it is, anything else is a constant texel.  Every mesh that carries such a BSDF needs texture coordinates."""
     _type_name = "MicrofacetBSDF"
 
-    def __init__(self, specular_reflectance=None, diffuse_reflectance=None, roughness=None):
+    def __init__(self, specular_reflectance=None, diffuse_reflectance=None, roughness=None, normal_map=None):
         super().__init__()
         self.specular_reflectance = specular_reflectance if isinstance(specular_reflectance, Bitmap3fD) else Bitmap3fD(
             0.04 if specular_reflectance is None else specular_reflectance)
         self.diffuse_reflectance = diffuse_reflectance if isinstance(diffuse_reflectance, Bitmap3fD) else Bitmap3fD(
             0.5 if diffuse_reflectance is None else diffuse_reflectance)
         self.roughness = roughness if isinstance(roughness, Bitmap1fD) else Bitmap1fD(0.5 if roughness is None else roughness)
+        self.normal_map = normal_map if normal_map is None or isinstance(normal_map, Bitmap3fD) else Bitmap3fD(normal_map)
 
     def to_string(self):
         return "MicrofacetBSDF[id=%s]" % self.id
@@ -1108,6 +1113,10 @@ class Scene(Object):
                 child = _find_child(node, names, True)          # a missing child keeps the constructor's default
                 if child is not None:
                     _load_texture(child, bitmap, base_dir)
+            child = _find_child(node, {"normalMap", "normal_map"}, True)          # a missing child: no normal map
+            if child is not None:
+                b.normal_map = Bitmap3fD((0.5, 0.5, 1.0))
+                _load_texture(child, b.normal_map, base_dir)
         else:
             raise RuntimeError("Unsupported BSDF: " + str(t))
         b.id = bid
@@ -1324,6 +1333,8 @@ class Scene(Object):
                      put(b.eta) + put(b.k))
             elif isinstance(b, MicrofacetBSDF):          # slots: kd, roughness, -, F0, - (include/psdr_hip.h)
                 r = ([_abi.BSDF_MICROFACET] + put(b.diffuse_reflectance) + put(b.roughness) + [0, 1, 1] + put(b.specular_reflectance) + [0, 1, 1])
+                if b.normal_map is not None:                 # ... with a normal map in the last slot: a type of its own
+                    r = [_abi.BSDF_MICROFACET_NORMAL] + r[1:13] + put(b.normal_map)
             else:
                 raise RuntimeError("Unsupported BSDF: " + b.type_name())
             rec.append(r)
