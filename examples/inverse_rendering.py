@@ -6,6 +6,7 @@
     python examples/inverse_rendering.py envmap       # recover the environment map's pixels under a metal bunny
     python examples/inverse_rendering.py svbrdf       # recover albedo and roughness maps of a quad from three flash photographs (CollocatedIntegrator)
     python examples/inverse_rendering.py svbrdf --normals     # ... of a quad with a bumpy normal map: albedo, roughness and normals
+    python examples/inverse_rendering.py svbrdf --height      # ... of a quad with a relief: albedo, roughness and a height map
     python examples/inverse_rendering.py shape        # recover a displaced sphere's vertices, one by one, through psdr_cuda.LargeSteps
 
 Needs an MI355X (the render path has no CPU fallback)."""
@@ -103,24 +104,30 @@ SVBRDF_XML = """<scene version="0.5.0">
 </scene>"""
 
 
-def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False):
+def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False, height=False):
     """A quad with map_res x map_res kd and roughness maps (MicrofacetBSDF, F0 known) photographed with a flash at the camera under three tilts -- one quad
     transformed three times, the maps shared.  The diffuse lobe is seen at every tilt, the specular lobe only near normal incidence, so the two maps separate by
     angle.  Adam on both maps from a flat start; the flash's intensity brings the pixel values (1 / distance^2 = 1e-6) to order 0.1.
     normals (--normals): the target quad also carries a bumpy tangent-space normal map (leaning up to about 25 degrees) and the loop recovers kd, roughness AND
-    the normal map, started flat.  Tilts about one axis leave the sign of the normal's component along that axis open, so the third view tilts about x."""
+    the normal map, started flat.  Tilts about one axis leave the sign of the normal's component along that axis open, so the third view tilts about x.
+    height (--height): the target quad carries a height map instead (texels in [0, 1], 2 world units per unit of height: slopes up to about 0.5 on the 16 x 16 cells of the
+    160 x 160 quad) and the loop recovers kd, roughness and the height map, started flat, from a head-on view and one tilt about each axis.  A height field has one number per texel
+    and its slopes are integrable by construction; a constant offset cannot be observed, so the error is reported with each map's mean removed."""
     rng = np.random.default_rng(3)
     kd_true = rng.uniform(0.2, 0.8, (map_res * map_res, 3)).astype(np.float32)
     r_true = rng.uniform(0.3, 0.6, map_res * map_res).astype(np.float32)
     integ = psdr_cuda.CollocatedIntegrator(1e6)
+    if height:
+        tilts = ((0.0, 0.0), (35.0, 0.0), (0.0, 35.0))          # head-on (the specular lobe: roughness), about y and about x (the sign of each slope)
+        h_true = rng.uniform(0.0, 1.0, map_res * map_res).astype(np.float32)
     if normals:
         tilts = ((35.0, 0.0), (-35.0, 0.0), (0.0, 35.0))          # (about y, about x)
         v_true = np.concatenate([rng.uniform(-0.35, 0.35, (map_res * map_res, 2)), np.ones((map_res * map_res, 1))], axis=1)
         n_true = ((v_true + 1.0) / 2.0).astype(np.float32)          # the image encoding: texel = (v + 1) / 2
 
-    def view(tilt, spp_, kd, rough, nm=None):
+    def view(tilt, spp_, kd, rough, nm=None, hm=None):
         sc = psdr_cuda.Scene()
-        if normals:
+        if normals or height:
             sc.load_string((SVBRDF_XML % tilt[0]).replace('y="1"/><translate', 'y="1"/><rotate angle="%g" x="1"/><translate' % tilt[1]), False)
         else:
             sc.load_string(SVBRDF_XML % tilt, False)
@@ -131,11 +138,14 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
         b.diffuse_reflectance.data, b.roughness.data = kd, rough
         if nm is not None:
             b.normal_map = psdr_cuda.Bitmap3fD(map_res, map_res, nm)
+        if hm is not None:
+            b.height_map = psdr_cuda.Bitmap1fD(map_res, map_res, hm)
+            b.height_scale = psdr_cuda.Bitmap1fD(2.0)
         return sc
     targets = []
     for tilt in tilts:
         ref = view(tilt, 256, Vector3fD(torch.as_tensor(kd_true, device="cuda")), FloatD(torch.as_tensor(r_true, device="cuda")),
-                   Vector3fD(torch.as_tensor(n_true, device="cuda")) if normals else None)
+                   Vector3fD(torch.as_tensor(n_true, device="cuda")) if normals else None, FloatD(torch.as_tensor(h_true, device="cuda")) if height else None)
         ref.configure()
         targets.append(integ.renderC(ref).torch().clone())
     kd = Vector3fD(torch.full((map_res * map_res, 3), 0.5, device="cuda"))
@@ -148,7 +158,12 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
         nm = Vector3fD(torch.tensor([[0.5, 0.5, 1.0]], device="cuda").repeat(map_res * map_res, 1))
         ek.set_requires_gradient(nm)
         params.append(nm.t)
-    views = [view(tilt, spp, kd, rough, nm) for tilt in tilts]
+    hm = None
+    if height:
+        hm = FloatD(torch.full((map_res * map_res,), 0.5, device="cuda"))
+        ek.set_requires_gradient(hm)
+        params.append(hm.t)
+    views = [view(tilt, spp, kd, rough, nm, hm) for tilt in tilts]
     opt = torch.optim.Adam(params, lr=0.03)
 
     def angle():
@@ -156,9 +171,14 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
         a, b = a / np.linalg.norm(a, axis=1, keepdims=True), b / np.linalg.norm(b, axis=1, keepdims=True)
         return float(np.degrees(np.arccos(np.clip((a * b).sum(1), -1.0, 1.0))).mean())
 
+    def relief():
+        a, b = hm.numpy().reshape(-1).astype(np.float64), h_true.astype(np.float64)
+        return float(np.abs((a - a.mean()) - (b - b.mean())).mean())
+
     def report():
-        return "mean texel error: kd %.4f, roughness %.4f%s" % (float(np.abs(kd.numpy() - kd_true).mean()), float(np.abs(rough.numpy().reshape(-1) - r_true).mean()),
-                                                               ", mean angular error of the normals %.2f degrees" % angle() if normals else "")
+        return "mean texel error: kd %.4f, roughness %.4f%s%s" % (float(np.abs(kd.numpy() - kd_true).mean()), float(np.abs(rough.numpy().reshape(-1) - r_true).mean()),
+                                                                 ", mean angular error of the normals %.2f degrees" % angle() if normals else "",
+                                                                 ", height (means removed) %.4f" % relief() if height else "")
     print("  start     %s" % report())
     t0 = time.perf_counter()
     for it in range(steps):
@@ -236,7 +256,9 @@ def shape():
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "albedo"
-    if which == "svbrdf" and "--normals" in sys.argv[2:]:
+    if which == "svbrdf" and "--height" in sys.argv[2:]:
+        svbrdf(height=True)
+    elif which == "svbrdf" and "--normals" in sys.argv[2:]:
         svbrdf(normals=True)
     else:
         {"albedo": albedo, "translation": translation, "envmap": envmap, "svbrdf": svbrdf, "shape": shape}[which]()

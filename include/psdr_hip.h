@@ -68,6 +68,13 @@ extern "C" {
    tri_uv rows) made orthogonal to n, t' = n x s'.  Needs tri_uv: the render entry points return an error for a scene that announces the type and has
    none.  Served like PSDR_BSDF_MICROFACET: PSDR_INTEGRATOR_COLLOCATED only. */
 #define PSDR_BSDF_MICROFACET_NORMAL 3
+/* MicrofacetBSDF with a height map (build-defined): the record of PSDR_BSDF_MICROFACET plus a 1-channel height map's
+   (offset, width, height) in PSDR_SLOT_K and its scale's (offset, 1, 1) in PSDR_SLOT_ALPHA_V -- one texel, world length per unit of height.  The
+   lobes are evaluated about n' = normalize(n - scale (h_u g_u + h_v g_v)): (h_u, h_v) the exact gradient of the bilinear map at the hit's uv,
+   (g_u, g_v) the dual basis in the shading plane of the triangle's derivatives along u and v (from its three tri_uv rows).  Needs tri_uv like
+   PSDR_BSDF_MICROFACET_NORMAL ("a height map needs texture coordinates") and is served like it: PSDR_INTEGRATOR_COLLOCATED only.  A record carries
+   a normal map or a height map, never both. */
+#define PSDR_BSDF_MICROFACET_HEIGHT 4
 /* bsdf_rec parameter slots: slot s occupies words 1+3*s .. 3+3*s */
 #define PSDR_SLOT_REFLECTANCE 0 /* Diffuse::m_reflectance / RoughConductor::m_specular_reflectance (3 ch) */
 #define PSDR_SLOT_ALPHA_U     1 /* 1 ch */
@@ -80,7 +87,10 @@ extern "C" {
      PSDR_SLOT_ETA          specular_reflectance F0 (3 ch)
    PSDR_SLOT_ALPHA_V and PSDR_SLOT_K are unused and hold (offset, width, height) = (0, 1, 1).
    PSDR_BSDF_MICROFACET_NORMAL reads the same three and
-     PSDR_SLOT_K            normal_map (3 ch) */
+     PSDR_SLOT_K            normal_map (3 ch)
+   PSDR_BSDF_MICROFACET_HEIGHT reads the same three and
+     PSDR_SLOT_K            height_map (1 ch)
+     PSDR_SLOT_ALPHA_V      height_scale (1 ch, 1 x 1) */
 
 /* cam[] layout (PerspectiveCamera, src/sensor/perspective.cpp:11-33), row-major 4x4 */
 #define PSDR_CAM_SAMPLE_TO_CAMERA  0
@@ -162,7 +172,7 @@ typedef struct psdr_scene_desc {
        Bits that are clear MUST be right: a cleared type is evaluated as diffuse.
        Bit PSDR_BSDF_MICROFACET (2) announces a MicrofacetBSDF record.  That type is never "unknown": with material_mask == 0 the caller
        promises that no PSDR_BSDF_MICROFACET record is present.  Bit PSDR_BSDF_MICROFACET_NORMAL (3) announces a normal-mapped one in the same way
-       (never "unknown" either) and selects the same kernels as bit 2. */
+       (never "unknown" either) and selects the same kernels as bit 2; bit PSDR_BSDF_MICROFACET_HEIGHT (4) does the same for a height-mapped one. */
     uint32_t       material_mask;
     /* [E][2] global triangle ids of the one or two faces adjacent to every secondary edge (second = -1 on a
        boundary edge), or NULL.  Not in the reference's SecondaryEdgeInfo (edge.h:27-65): the two rays that

@@ -160,7 +160,7 @@ PSDR_HD Vec3f collocated_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, co
     const Vec3f a{isfinite(result.x) ? adj.x : 0.f, isfinite(result.y) ? adj.y : 0.f, isfinite(result.z) ? adj.z : 0.f};
     VertexAdj va0; va0.clear();
     Vec3f a_wo(0.f);
-    NormalMapAdj nx; nx.clear();                                         // a normal-mapped MicrofacetBSDF: adjoints of the shading frame and of e1, e2 (dp_du)
+    NormalMapAdj nx; nx.clear();                                         // a normal- or height-mapped MicrofacetBSDF: adjoints of the shading frame and of e1, e2 (dp_du / p_u, p_v)
     colloc_bsdf_eval_vjp(sink, sc, tv0, brev, its, its.wi, a * inv_d2, va0.wi, a_wo, va0.u, va0.v, nx);
     acc(va0.wi, a_wo);                                                   // wo = wi
     constexpr bool kNormalMaps = (Sink::flags & kSceneRough) != 0;       // (the type is compiled into the rough flag sets only)

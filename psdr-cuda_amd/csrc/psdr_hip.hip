@@ -607,6 +607,8 @@ int check_microfacet(const psdr_scene_s *h, const psdr_render_opts *o) {
         return fail("MicrofacetBSDF is evaluated by the CollocatedIntegrator only");
     // PSDR_BSDF_MICROFACET_NORMAL builds its tangent frame from the triangle's texture coordinates: without the table there is no defined value
     if ((h->desc.material_mask & (1u << PSDR_BSDF_MICROFACET_NORMAL)) != 0 && h->desc.tri_uv == nullptr) return fail("a normal map needs texture coordinates");
+    // ... and PSDR_BSDF_MICROFACET_HEIGHT its surface-gradient basis
+    if ((h->desc.material_mask & (1u << PSDR_BSDF_MICROFACET_HEIGHT)) != 0 && h->desc.tri_uv == nullptr) return fail("a height map needs texture coordinates");
     return 0;
 }
 
@@ -1141,7 +1143,7 @@ int psdr_scene_set_tables(psdr_scene_t h, const psdr_scene_desc *desc) {
     h->desc = d;
     // material_mask = 0: unknown -> serve every BSDF type
     // ... except MicrofacetBSDF, which only its own bit announces (psdr_hip.h); it lives in the GGX code of the collocated rough flag sets
-    h->has_microfacet = (d.material_mask & ((1u << PSDR_BSDF_MICROFACET) | (1u << PSDR_BSDF_MICROFACET_NORMAL))) != 0;          // (with or without a normal map)
+    h->has_microfacet = (d.material_mask & ((1u << PSDR_BSDF_MICROFACET) | (1u << PSDR_BSDF_MICROFACET_NORMAL) | (1u << PSDR_BSDF_MICROFACET_HEIGHT))) != 0;          // (with or without a normal or a height map)
     h->has_rough = d.material_mask == 0 || (d.material_mask & (1u << PSDR_BSDF_ROUGHCONDUCTOR)) != 0 || h->has_microfacet;
     h->have_tables = true;
     h->pg_cmf = h->pg_pmf = nullptr; h->pg_sum = 0.f;          // segment B's guiding grid belongs to the tables it was built for (psdr_scene_set_path_guide)

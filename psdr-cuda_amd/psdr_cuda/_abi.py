@@ -22,7 +22,7 @@ CAM_WORDS = 64
 ENV_WORDS = 32
 TRI_FACE_NORMALS = 0x40000000
 
-BSDF_DIFFUSE, BSDF_ROUGHCONDUCTOR, BSDF_MICROFACET, BSDF_MICROFACET_NORMAL = 0, 1, 2, 3
+BSDF_DIFFUSE, BSDF_ROUGHCONDUCTOR, BSDF_MICROFACET, BSDF_MICROFACET_NORMAL, BSDF_MICROFACET_HEIGHT = 0, 1, 2, 3, 4
 SLOT_REFLECTANCE, SLOT_ALPHA_U, SLOT_ALPHA_V, SLOT_ETA, SLOT_K = range(5)
 CAM_SAMPLE_TO_CAMERA, CAM_TO_WORLD, CAM_WORLD_TO_SAMPLE, CAM_POS, CAM_DIR, CAM_INV_AREA = 0, 16, 32, 48, 51, 54
 INTEGRATOR_DIRECT, INTEGRATOR_PATH, INTEGRATOR_FIELD, INTEGRATOR_COLLOCATED = 0, 1, 2, 3

@@ -17,7 +17,7 @@ import torch
 import enoki as ek
 from . import _abi
 from .core import Object, psdr_assert, Vector3fC, Vector3fD, HyperCubeDistribution3f
-from .scene import make_desc, MicrofacetBSDF, MICROFACET_COLLOCATED_ONLY, NORMAL_MAP_NEEDS_UV
+from .scene import make_desc, MicrofacetBSDF, MICROFACET_COLLOCATED_ONLY, NORMAL_MAP_NEEDS_UV, HEIGHT_MAP_NEEDS_UV
 
 _AD_KEYS = _abi.TANGENT_FIELDS
 
@@ -332,6 +332,8 @@ class Integrator(Object):
         # a normal map's tangent frame follows the texture coordinates: a mesh without them has no defined value (the C ABI refuses a scene without the table)
         if any(isinstance(m.bsdf, MicrofacetBSDF) and m.bsdf.normal_map is not None and not m.m_has_uv for m in scene.m_meshes):
             raise RuntimeError(NORMAL_MAP_NEEDS_UV)
+        if any(isinstance(m.bsdf, MicrofacetBSDF) and m.bsdf.height_map is not None and not m.m_has_uv for m in scene.m_meshes):          # ... and so does a height map's basis
+            raise RuntimeError(HEIGHT_MAP_NEEDS_UV)
 
     # ---- public API (src/psdr.cpp:282-285) -------------------------------------------
     def renderC(self, scene, sensor_id=0):

@@ -103,6 +103,8 @@ RoughConductorBSDF = RoughConductor
 
 MICROFACET_COLLOCATED_ONLY = "MicrofacetBSDF is evaluated by the CollocatedIntegrator only"
 NORMAL_MAP_NEEDS_UV = "a normal map needs texture coordinates"
+HEIGHT_MAP_NEEDS_UV = "a height map needs texture coordinates"
+NORMAL_OR_HEIGHT = "a MicrofacetBSDF takes a normal map or a height map, not both"
 
 
 class MicrofacetBSDF(BSDF):
@@ -112,17 +114,25 @@ class MicrofacetBSDF(BSDF):
     CollocatedIntegrator renders it, DirectIntegrator and PathTracer raise.
     normal_map: a tangent-space normal map in the image encoding -- texel c decodes to 2c - 1, (0.5, 0.5, 1) is "no perturbation" -- in
     the frame (direction of increasing u made orthogonal to the shading normal, n x that, the shading normal); None: no map, the record of section 14.  A
-    Bitmap3fD is kept as it is, anything else is a constant texel.  Every mesh that carries such a BSDF needs texture coordinates."""
+    Bitmap3fD is kept as it is, anything else is a constant texel.  Every mesh that carries such a BSDF needs texture coordinates.
+    height_map, height_scale: a 1-channel height field h(u, v) and the world length of one unit of it (a 1 x 1 Bitmap1fD, default 1).  The
+    lobes are evaluated about the normal of the surface displaced by height_scale x h along the shading normal, to first order: the map's exact bilinear
+    gradient in the surface-gradient basis of the triangle's texture coordinates.  None: no map.  A Bitmap1fD is kept as it is, anything else is a constant
+    texel (a constant height is a flat surface).  The mesh needs texture coordinates, as for a normal map; a BSDF takes one of the two maps, not both."""
     _type_name = "MicrofacetBSDF"
 
-    def __init__(self, specular_reflectance=None, diffuse_reflectance=None, roughness=None, normal_map=None):
+    def __init__(self, specular_reflectance=None, diffuse_reflectance=None, roughness=None, normal_map=None, height_map=None, height_scale=1.0):
         super().__init__()
         self.specular_reflectance = specular_reflectance if isinstance(specular_reflectance, Bitmap3fD) else Bitmap3fD(
             0.04 if specular_reflectance is None else specular_reflectance)
         self.diffuse_reflectance = diffuse_reflectance if isinstance(diffuse_reflectance, Bitmap3fD) else Bitmap3fD(
             0.5 if diffuse_reflectance is None else diffuse_reflectance)
         self.roughness = roughness if isinstance(roughness, Bitmap1fD) else Bitmap1fD(0.5 if roughness is None else roughness)
+        if normal_map is not None and height_map is not None:
+            raise RuntimeError(NORMAL_OR_HEIGHT)
         self.normal_map = normal_map if normal_map is None or isinstance(normal_map, Bitmap3fD) else Bitmap3fD(normal_map)
+        self.height_map = height_map if height_map is None or isinstance(height_map, Bitmap1fD) else Bitmap1fD(height_map)
+        self.height_scale = height_scale if isinstance(height_scale, Bitmap1fD) else Bitmap1fD(1.0 if height_scale is None else height_scale)
 
     def to_string(self):
         return "MicrofacetBSDF[id=%s]" % self.id
@@ -1117,6 +1127,15 @@ class Scene(Object):
             if child is not None:
                 b.normal_map = Bitmap3fD((0.5, 0.5, 1.0))
                 _load_texture(child, b.normal_map, base_dir)
+            child = _find_child(node, {"heightMap", "height_map"}, True)          # a missing child: no height map
+            if child is not None:
+                if b.normal_map is not None:
+                    raise RuntimeError(NORMAL_OR_HEIGHT)
+                b.height_map = Bitmap1fD(0.0)
+                _load_texture(child, b.height_map, base_dir)
+            child = _find_child(node, {"heightScale", "height_scale"}, True)
+            if child is not None:
+                _load_texture(child, b.height_scale, base_dir)
         else:
             raise RuntimeError("Unsupported BSDF: " + str(t))
         b.id = bid
@@ -1335,6 +1354,11 @@ class Scene(Object):
                 r = ([_abi.BSDF_MICROFACET] + put(b.diffuse_reflectance) + put(b.roughness) + [0, 1, 1] + put(b.specular_reflectance) + [0, 1, 1])
                 if b.normal_map is not None:                 # ... with a normal map in the last slot: a type of its own
                     r = [_abi.BSDF_MICROFACET_NORMAL] + r[1:13] + put(b.normal_map)
+                if b.height_map is not None:                 # ... with a height map there and its scale in the free 1-channel slot: another type
+                    if b.normal_map is not None:
+                        raise RuntimeError(NORMAL_OR_HEIGHT)
+                    psdr_assert(tuple(b.height_scale.resolution) == (1, 1), "height_scale is one texel")
+                    r = [_abi.BSDF_MICROFACET_HEIGHT] + r[1:7] + put(b.height_scale) + r[10:13] + put(b.height_map)
             else:
                 raise RuntimeError("Unsupported BSDF: " + b.type_name())
             rec.append(r)
