@@ -96,8 +96,8 @@ __global__ __launch_bounds__(kB) void k_tri_rows_rev_vn(int T, const int32_t *__
         if (an.x == 0.f && an.y == 0.f && an.z == 0.f) continue;
         const int i = faces[3 * t + k];
         const V3 s = ld3(vsum + 3 * (size_t) i);
-        const float len = sqrtf(dot(s, s));
-        add3(a_vsum + 3 * (size_t) i, normalize_vjp(s * (1.f / len), len, an));
+        const float len = sqrtf(dot(s, s)), inv = len > 0.f ? 1.f / len : 0.f;      // a zero normal sum: no adjoint, as normalize_jvp gives no tangent
+        add3(a_vsum + 3 * (size_t) i, normalize_vjp(s * inv, len, an));
     }
 }
 // adjoint, pass 2: per face, everything that flows into its three vertices
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kB) void k_tri_rows_rev(int T, const float *__restr
     const float *ar = a_rows + (size_t) t * stride;
     // adjoint of c = cross(e1, e2): from the three vertex sums, the face normal c / |c| and the area |c| / 2
     V3 ac = ld3(a_vsum + 3 * (size_t) i0) + ld3(a_vsum + 3 * (size_t) i1) + ld3(a_vsum + 3 * (size_t) i2);
-    const V3 fn = c * (1.f / len);
+    const V3 fn = c * (len > 0.f ? 1.f / len : 0.f);          // a degenerate face: no adjoint through its normal and area, as k_tri_rows_jvp gives no tangent
     ac = ac + normalize_vjp(fn, len, ld3(ar + 18)) + fn * (0.5f * ar[21]);
     // c = e1 x e2:  a_e1 = e2 x a_c,  a_e2 = a_c x e1
     const V3 ae1 = ld3(ar + 3) + cross(e2, ac), ae2 = ld3(ar + 6) + cross(ac, e1);
@@ -569,13 +569,13 @@ int psdr_geo_tri_rows_jvp(int32_t V, int32_t T, const float *v, const int32_t *f
     return 0;
 }
 int psdr_geo_sec_edges_fwd(int32_t E, const int32_t *edges, const float *v, const float *rows, int32_t row_stride, float *info, uint8_t *keep, void *stream) {
-    if (E <= 0 || !edges || !v || !rows || !info || !keep) return psdr_host::fail("psdr_geo_sec_edges_fwd: invalid argument");
+    if (E <= 0 || !edges || !v || !rows || row_stride < 22 || !info || !keep) return psdr_host::fail("psdr_geo_sec_edges_fwd: invalid argument");
     hipLaunchKernelGGL(k_sec_edges, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, v, rows, row_stride, info, keep);
     TAB_TRY(hipGetLastError());
     return 0;
 }
 int psdr_geo_sec_edges_rev(int32_t E, const int32_t *edges, const float *a_info, float *a_v, float *a_rows, int32_t row_stride, void *stream) {
-    if (E <= 0 || !edges || !a_info || !a_v || !a_rows) return psdr_host::fail("psdr_geo_sec_edges_rev: invalid argument");
+    if (E <= 0 || !edges || !a_info || !a_v || !a_rows || row_stride < 22) return psdr_host::fail("psdr_geo_sec_edges_rev: invalid argument");
     hipLaunchKernelGGL(k_sec_edges_rev, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, a_info, a_v, a_rows, row_stride);
     TAB_TRY(hipGetLastError());
     return 0;
@@ -588,7 +588,7 @@ int psdr_geo_sec_edges_jvp(int32_t E, const int32_t *edges, const float *t_v, co
 }
 int psdr_geo_prim_edges_fwd(int32_t E, const int32_t *edges, const uint8_t *face_normals, const float *v, const float *rows, int32_t row_stride,
                             const float *cam22, float *rows8, float *z4, uint8_t *keep, void *stream) {
-    if (E <= 0 || !edges || !face_normals || !v || !rows || !cam22 || !rows8 || !z4 || !keep) return psdr_host::fail("psdr_geo_prim_edges_fwd: invalid argument");
+    if (E <= 0 || !edges || !face_normals || !v || !rows || row_stride < 22 || !cam22 || !rows8 || !z4 || !keep) return psdr_host::fail("psdr_geo_prim_edges_fwd: invalid argument");
     hipLaunchKernelGGL(k_prim_edges, grid(E), dim3(kB), 0, (hipStream_t) stream, E, edges, face_normals, v, rows, row_stride, cam22, rows8, z4, keep);
     TAB_TRY(hipGetLastError());
     return 0;
