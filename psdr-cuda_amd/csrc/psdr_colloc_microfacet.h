@@ -7,7 +7,8 @@
 // r = PSDR_SLOT_ALPHA_U, F0 = PSDR_SLOT_ETA.  Where D's cut-off answers zero -- alpha = 0 among the cases -- the specular lobe is zero and the value is
 // the diffuse lobe.
 // The model is an evaluation and its adjoint, no sample / pdf: the CollocatedIntegrator (psdr_collocated.h) evaluates f at ONE direction pair, wo = wi (there
-// h = wi and F = F0), and is the only integrator that serves the type.  Both functions take a general wo all the same.
+// h = wi and F = F0), and is the only integrator that serves the type.  The value (microfacet_any_eval) and its adjoint
+// (microfacet_eval_vjp, microfacet_mapped_eval_vjp) take a general wo all the same.
 // PSDR_BSDF_MICROFACET_NORMAL is the same record plus a tangent-space normal map in PSDR_SLOT_K: the lobes are evaluated about a
 // normal n' turned away from the shading normal in a frame whose tangent follows the texture's u axis (normal_map_frame below).
 // PSDR_BSDF_MICROFACET_HEIGHT is the same record plus a 1-channel height map in PSDR_SLOT_K and its scale in PSDR_SLOT_ALPHA_V: n' is the
@@ -33,11 +34,6 @@ PSDR_HD Vec3<M> microfacet_lobes(const SceneView &sc, const TVT &tv, const Bsdf<
     const M t = 1.f - dot(wi_m, H);
     const M w = sqr(sqr(t)) * t;
     return {diffuse.x + (F0.x + (1.f - F0.x) * w) * res, diffuse.y + (F0.y + (1.f - F0.y) * w) * res, diffuse.z + (F0.z + (1.f - F0.z) * w) * res};
-}
-template <class G, class M, class TVT>
-PSDR_HD Vec3<M> microfacet_eval(const SceneView &sc, const TVT &tv, const Bsdf<G, M> &b, const Its<G> &its, const Vec3<G> &wo, bool active) {
-    if (!(active && val(its.wi.z) > 0.f && val(wo.z) > 0.f)) return zero3<M>();
-    return microfacet_lobes<G, M>(sc, tv, b, its, to_m3<M>(its.wi), to_m3<M>(wo));
 }
 
 // Adjoint of value = microfacet_lobes(its, wi, wo): af (RGB) -> awi, awo, the texels of the three maps (through the sink), a_uv.
@@ -297,17 +293,6 @@ PSDR_HD void microfacet_mapped_eval_vjp(Sink &sink, const SceneView &sc, const T
     if (flat) { acc_finite(x.n, an1); return; }
     if (height) height_map_frame_vjp(sink, sc, b, its, hm, an1, x, auvx, auvy);
     else normal_map_frame_vjp(sink, sc, b, its, nm, an1, x, auvx, auvy);
-}
-// ... by record type
-template <class Sink, class TVT>
-PSDR_HD void microfacet_normal_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0, const Bsdf<float, float> &b, const Its<float> &its, const Vec3f &wo,
-                                        const Vec3f &af, Vec3f &awi, Vec3f &awo, NormalMapAdj &x, float &auvx, float &auvy) {
-    microfacet_mapped_eval_vjp(sink, sc, tv0, b, its, wo, af, false, awi, awo, x, auvx, auvy);
-}
-template <class Sink, class TVT>
-PSDR_HD void microfacet_height_eval_vjp(Sink &sink, const SceneView &sc, const TVT &tv0, const Bsdf<float, float> &b, const Its<float> &its, const Vec3f &wo,
-                                        const Vec3f &af, Vec3f &awi, Vec3f &awo, NormalMapAdj &x, float &auvx, float &auvy) {
-    microfacet_mapped_eval_vjp(sink, sc, tv0, b, its, wo, af, true, awi, awo, x, auvx, auvy);
 }
 
 // The collocated estimator's BSDF value and its adjoint: MicrofacetBSDF by the record's type where the instance carries the GGX code (ROUGH), Bsdf::eval /

@@ -1,7 +1,7 @@
 // hostcheck_collocated.cpp -- TEST-ONLY harness: the CollocatedIntegrator's estimator (csrc/psdr_collocated.h, PSDR_HD functions) run on the host, slot by slot,
 // so that `-m "not gpu"` tests can check it where no GPU exists and the GPU tests have a reference the oracle does not offer (the reference snapshot has no such
 // integrator).  A library of its own (libhostcheck_collocated.so), as hostcheck_path_sedge.cpp is for its header.  Never imported by the psdr_cuda package and
-// not a fallback: the render path only ever executes these functions inside HIP kernels.  tests/hostcheck/collocated_san.cpp includes this file into a
+// not a fallback: the render path only ever executes these functions inside HIP kernels.  tests/hostcheck/colloc_san.cpp includes this file into a
 // stand-alone program for the host sanitizers.
 #include "host_common.h"
 #include "../../psdr-cuda_amd/csrc/psdr_collocated.h"

@@ -4,6 +4,7 @@ marshalling every front end of a host-check library needs.  Only the standard li
 package are imported by the functions that hand tables over."""
 import ctypes as C
 import os
+import subprocess
 import sys
 
 TESTS = os.path.dirname(os.path.abspath(__file__))
@@ -23,6 +24,24 @@ def load(name):
     if name not in _loaded:
         _loaded[name] = C.CDLL(build(name))
     return _loaded[name]
+
+
+def san_program(name, extra_deps):
+    """The stand-alone program tests/hostcheck/<name>.cpp (its own main, run as a child process, never loaded into Python) built with the host sanitizers;
+    rebuilt when its source or one of `extra_deps` is newer than the executable.  Returns the executable's path."""
+    exe, src = os.path.join(HC_DIR, name), os.path.join(HC_DIR, name + ".cpp")
+    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in list(extra_deps) + [src]):
+        tmp = "%s.%d.tmp" % (exe, os.getpid())          # the test files that share the program may run in several processes: each builds its own file, the rename is atomic
+        cmd = ["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-pthread", src, "-o", tmp]
+        san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+        r = subprocess.run(cmd + san, capture_output=True, text=True)
+        if r.returncode != 0 and ("libclang_rt" in r.stderr or "sanitizer" in r.stderr.lower()):
+            # no host sanitizer runtime beside this compiler: the program still runs the same functions over the same tables, without the instrumentation
+            print("%s: built WITHOUT the sanitizers, the compiler's host runtime for them is missing:\n" % name + r.stderr[-800:])
+            r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, "%s does not compile:\n" % name + r.stderr[-3000:]
+        os.replace(tmp, exe)
+    return exe
 
 
 def host_threads():

@@ -9,26 +9,26 @@ import torch
 import enoki as ek
 import psdr_cuda
 from collocated_helpers import colloc_opts, host_colloc_render, host_colloc_rev
-from colloc_height_helpers import (NEEDS_UV, ONE_CELL, RECOVERY_INTENSITY, RECOVERY_LR, RECOVERY_STEPS, RECOVERY_TILTS, height_record, height_width, height_xml, mixed_xml,
-                                   named_scene, quad_xml, recovery_errors, recovery_start, recovery_truth, recovery_xml, scene)
-from colloc_microfacet_helpers import MESSAGE
+from colloc_microfacet_helpers import KINDS, MESSAGE, ONE_CELL, RECOVERY, height_xml, map_words, mixed_xml, named_scene, record, scene, uv_quad_xml
 from enoki.cuda_autodiff import Float32 as FloatD, Vector3f as Vector3fD
 from helpers import GpuScene, dot_tables, isolated_pixels_unbiased, random_tangents, rel_l2
 from psdr_cuda import _abi
 
 pytestmark = pytest.mark.gpu
+MIXED_IDS = ("d", "c", "m", "n", "h")          # the quads of mixed_xml: record types 0 .. 4
+R = RECOVERY["height"]
 
 
 def _scene(name, res, spp, sppe=0):
     """the scene forms of the host file's forward = reverse test (rotated-UV quad, room without a tree, bunny with one), the quad with the one-cell map, the
     mirrored-UV quad and the scene of the five record types; 4 x 4 maps on every bilinear slot"""
     if name == "one-cell":
-        return scene(quad_xml(height_xml(0.3), 30.0), res, spp, sppe, uv="rot37", height=ONE_CELL, map_res=(2, 2), textured=True)
+        return scene(uv_quad_xml(height_xml(0.3), 30.0), res, spp, sppe, uv="rot37", height=ONE_CELL, map_res=(2, 2), textured=True)
     if name == "mirror":
-        return scene(quad_xml(height_xml(0.3), 30.0), res, spp, sppe, uv="mirror", height="random", textured=True)
+        return scene(uv_quad_xml(height_xml(0.3), 30.0), res, spp, sppe, uv="mirror", height="random", textured=True)
     if name == "mixed":
-        return scene(mixed_xml(), res, spp, sppe, uv="rot37", normal="random", height="random", textured=True)
-    return named_scene(name, res, spp, sppe)
+        return scene(mixed_xml(MIXED_IDS), res, spp, sppe, uv="rot37", normal="random", height="random", textured=True)
+    return named_scene("height", name, res, spp, sppe)
 
 
 @pytest.mark.parametrize("name,tree", [("one-cell", False), ("quad", False), ("mirror", False), ("room", False), ("bunny", True)])
@@ -54,12 +54,12 @@ def test_render_c_matches_the_harness(name, tree):
 
 def _height_sets(tb):
     """three tangent sets: random on the even height texels, random on the odd ones, one on the scale"""
-    row, off = height_record(tb)
+    row, off = record(tb, "height")
     rnd = random_tangents(tb, ["texels"], seed=2)["texels"]
     sets = []
     for first in (0, 1):
         t = torch.zeros_like(rnd)
-        idx = torch.arange(off["height"] + first, off["height"] + height_width(row), 2)
+        idx = torch.arange(off["height"] + first, off["height"] + map_words(row, "height"), 2)
         t[idx] = rnd[idx]
         sets.append({"texels": t})
     t = torch.zeros_like(rnd)
@@ -110,8 +110,8 @@ def test_reverse_equals_forward(name):
     names = ["tri_info", "texels", "cam_to_world", "prim_edge"]
     img_r, grads = g.render_d_rev(o, adj, want=names)
     _, host_grads = host_colloc_rev(tb, o, adj, want=names)
-    row, off = height_record(tb)
-    for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("height", height_width(row)), ("scale", 1)):
+    row, off = record(tb, "height")
+    for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("height", map_words(row, "height")), ("scale", 1)):
         assert np.abs(grads["texels"][off[key]:off[key] + width]).max() > 0, key
     for n in names:
         tan = random_tangents(tb, [n], seed=1)
@@ -146,7 +146,7 @@ def test_python_surface():
     g = GpuScene(tb)
     unit = g.render_c(colloc_opts(4))
     _, cg = g.render_d_rev(colloc_opts(4, 4), adj * np.array(inten, np.float32), want=["texels"])
-    _, off = height_record(tb)
+    _, off = record(tb, "height")
     for m, key in zip(maps, ("kd", "f0", "roughness", "height", "scale")):
         got = ek.gradient(m).numpy().reshape(-1)
         want = cg["texels"][off[key]:off[key] + got.size]
@@ -175,7 +175,7 @@ def test_error_returns():
     build.  A type-4 record in tables whose tri_uv is NULL: "a height map needs texture coordinates" from the three render entry points, no silent fallback.  The
     handle stays intact: with the table back, the CollocatedIntegrator renders what the harness renders."""
     light = '<ref id="m"/><emitter type="area"><rgb name="radiance" value="5, 5, 5"/></emitter>'          # (an emitter, so that "No Emitter!" is not the answer)
-    sc = scene(quad_xml(height_xml(0.3), 30.0).replace('<ref id="m"/>', light), 16, 4, 4, height="random")
+    sc = scene(uv_quad_xml(height_xml(0.3), 30.0).replace('<ref id="m"/>', light), 16, 4, 4, height="random")
     tb = sc.tables(0)
     assert tb["num_emitters"] == 1 and tb["material_mask"] == 16
     g = GpuScene(tb)
@@ -193,7 +193,7 @@ def test_error_returns():
     gb = GpuScene(bare)
     o = colloc_opts(4, 4)
     for call in (lambda: gb.render_c(o), lambda: gb.render_d_fwd(o, [tan]), lambda: gb.render_d_rev(o, adj, want=["texels"])):
-        with pytest.raises(RuntimeError, match=NEEDS_UV):
+        with pytest.raises(RuntimeError, match=KINDS["height"].needs_uv):
             call()
     with pytest.raises(RuntimeError, match=MESSAGE):          # the older message first
         gb.render_c(_abi.make_opts(integrator=_abi.INTEGRATOR_DIRECT, max_depth=1, spp=4))
@@ -205,7 +205,7 @@ def _recovery_scene(tilt, spp, kd, hm):
         b = sc.m_bsdfs[0]
         b.diffuse_reflectance.resolution = b.height_map.resolution = (4, 4)
         b.diffuse_reflectance.data, b.height_map.data = kd, hm
-    return scene(recovery_xml(tilt), 32, spp, 0, extra=maps)
+    return scene(R.xml(tilt), 32, spp, 0, extra=maps)
 
 
 def test_recover_albedo_and_height_maps():
@@ -214,20 +214,20 @@ def test_recover_albedo_and_height_maps():
     maps.  Condition: the mean kd texel error and the mean height texel error with each map's mean removed (a constant offset cannot be observed) both end
     below half of their start.  The step length (0.05) comes from the same loop over the host harness: kd 0.1507 -> 0.0202, height 0.2731 -> 0.0410 (at 0.02: 0.0242,
     0.0355; at 0.1: 0.0233, 0.0344); on the MI355X 0.0191 and 0.0411."""
-    kd_true, h_true = recovery_truth()
-    integ = psdr_cuda.CollocatedIntegrator(RECOVERY_INTENSITY)          # the quad is 1000 away: pixel values of order 0.1
+    kd_true, h_true = R.truth()
+    integ = psdr_cuda.CollocatedIntegrator(R.intensity)          # the quad is 1000 away: pixel values of order 0.1
     targets = []
-    for tilt in RECOVERY_TILTS:
+    for tilt in R.tilts:
         ref = _recovery_scene(tilt, 64, Vector3fD(torch.from_numpy(kd_true)), FloatD(torch.from_numpy(h_true)))
         targets.append(integ.renderC(ref).torch().clone())
-    kd0, h0 = recovery_start()
+    kd0, h0 = R.start()
     kd, hm = Vector3fD(torch.from_numpy(kd0)), FloatD(torch.from_numpy(h0))
     ek.set_requires_gradient(kd)
     ek.set_requires_gradient(hm)
-    scenes = [_recovery_scene(tilt, 4, kd, hm) for tilt in RECOVERY_TILTS]
-    start = recovery_errors(kd.numpy(), hm.numpy())
-    opt = torch.optim.Adam([kd.t, hm.t], lr=RECOVERY_LR)
-    for it in range(RECOVERY_STEPS):
+    scenes = [_recovery_scene(tilt, 4, kd, hm) for tilt in R.tilts]
+    start = R.errors(kd.numpy(), hm.numpy())
+    opt = torch.optim.Adam([kd.t, hm.t], lr=R.lr)
+    for it in range(R.steps):
         opt.zero_grad()
         for sc, target in zip(scenes, targets):
             sc.configure()
@@ -235,6 +235,6 @@ def test_recover_albedo_and_height_maps():
             ek.backward(ek.hmean(ek.hsum(ek.sqr(img - Vector3fD._wrap(target)))))
         opt.step()
         kd.t.data.clamp_(0.01, 0.99)
-    end = recovery_errors(kd.numpy(), hm.numpy())
+    end = R.errors(kd.numpy(), hm.numpy())
     print("height map recovery: mean kd texel error %.4f -> %.4f, mean-removed mean height error %.4f -> %.4f" % (start[0], end[0], start[1], end[1]))
     assert end[0] < 0.5 * start[0] and end[1] < 0.5 * start[1], (start, end)

@@ -12,20 +12,18 @@ import torch
 
 import enoki as ek
 import psdr_cuda
-from collocated_helpers import HC_DEPS, HC_DIR, _HEAD, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, xml_scene
-from colloc_height_helpers import (MIXED_IDS, NEEDS_UV, NOT_BOTH, ONE_CELL, SIGMA, closed_form_image, height_record, height_width, height_xml, mixed_xml, named_scene,
-                                   perturbed_normal64, quad_xml, scene)
-from colloc_microfacet_helpers import MESSAGE, microfacet_record, microfacet_xml, uv_quad_xml
-from colloc_microfacet_helpers import bunny_xml as plain_bunny_xml
-from colloc_normal_helpers import encode, normal_xml, quad
+from collocated_helpers import HC_DEPS, _HEAD, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, xml_scene
+from colloc_microfacet_helpers import (KINDS, MESSAGE, NOT_BOTH, ONE_CELL, SIGMA, bunny_xml, closed_form_image, encode, height_xml, map_words, microfacet_xml, mixed_xml,
+                                       named_scene, normal_xml, perturbed_normal64, quad, record, scene, uv_quad_xml)
 from enoki.cuda_autodiff import Float32 as FloatD
 from helpers import dot_tables, random_tangents, rel_l2, tangents_wrt
-from hostlibs import cpu_desc, write_tables_file
+from hostlibs import cpu_desc, san_program, write_tables_file
 from psdr_cuda import _abi
 
 RES, SPP = 16, 4
 TILTS, ROUGHNESS = (0.0, 30.0, 70.0), (0.3, 0.6)
 NAMES = ["texels", "tri_info", "cam_to_world", "prim_edge"]
+MIXED_IDS = ("d", "c", "m", "n", "h")          # the quads of mixed_xml: record types 0 .. 4
 
 
 # ---------------------------------------------------------------- 1. closed form
@@ -45,14 +43,14 @@ def test_closed_form(tilt, r, uv, case):
     Measured (rel-L2): 6.7e-8 .. 4.1e-7 at 0 degrees, 1.1e-7 .. 1.2e-7 at 30, 2.5e-7 .. 6.37e-7 at 70; the 2 x 2 and the 4 x 4 map alike (slopes below 0.5 keep wi'.z
     away from zero, unlike the 50-degree normals of section 15's 4 x 4 map)."""
     if case == "2x2":
-        sc = scene(quad_xml(height_xml(r), tilt), RES, SPP, uv=uv, height=ONE_CELL, map_res=(2, 2))
+        sc = scene(uv_quad_xml(height_xml(r), tilt), RES, SPP, uv=uv, height=ONE_CELL, map_res=(2, 2))
     else:
-        sc = scene(quad_xml(height_xml(r), tilt), RES, SPP, uv=uv, height="random")
+        sc = scene(uv_quad_xml(height_xml(r), tilt), RES, SPP, uv=uv, height="random")
     tb = sc.tables(0)
     assert tb["material_mask"] == 1 << _abi.BSDF_MICROFACET_HEIGHT
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
     img = host_colloc_render(tb, o)
-    ref = closed_form_image(tb, host_film_samples(tb, o), SPP)
+    ref = closed_form_image(tb, host_film_samples(tb, o), SPP, "height")
     assert (ref > 0).any() and (ref == 0).any()          # the quad and the background are both seen
     e = rel_l2(img, ref)
     print("height map closed form tilt %g r %g %s %s: rel-L2 %.2e" % (tilt, r, uv, case, e))
@@ -62,8 +60,8 @@ def test_closed_form(tilt, r, uv, case):
 def test_closed_form_tells_the_map():
     """the closed form itself tells the maps apart: the 4 x 4 image differs from the flat one by more than 1e-2"""
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
-    a = host_colloc_render(scene(quad_xml(height_xml(0.3), 30.0), RES, SPP, height="random").tables(0), o)
-    b = host_colloc_render(scene(quad_xml(height_xml(0.3), 30.0), RES, SPP).tables(0), o)
+    a = host_colloc_render(scene(uv_quad_xml(height_xml(0.3), 30.0), RES, SPP, height="random").tables(0), o)
+    b = host_colloc_render(scene(uv_quad_xml(height_xml(0.3), 30.0), RES, SPP).tables(0), o)
     assert rel_l2(a, b) > 1e-2
 
 
@@ -77,7 +75,7 @@ def test_ramp_equals_a_constant_normal_map(tilt, axis):
     taken from the tables).  Images to 2e-6 rel-L2.  Measured: 0 .. 1.65e-7."""
     k = 0.8
     tex = np.array([0.0, k, 0.0, k] if axis == "u" else [k, k, 0.0, 0.0], np.float32)          # (row 0 is v -> 1: the lookup flips v)
-    tbh = scene(quad_xml(height_xml(0.3), tilt), RES, SPP, height=tex, map_res=(2, 2)).tables(0)
+    tbh = scene(uv_quad_xml(height_xml(0.3), tilt), RES, SPP, height=tex, map_res=(2, 2)).tables(0)
     T = tbh["tri_info"].detach().cpu().numpy().astype(np.float64)[0]
     q = tbh["tri_uv"].detach().cpu().numpy().astype(np.float64).reshape(tbh["num_tris"], -1)[0, :6]
     e1, e2, n = T[3:6], T[6:9], T[18:21] / np.linalg.norm(T[18:21])
@@ -89,13 +87,13 @@ def test_ramp_equals_a_constant_normal_map(tilt, axis):
     hu, hv = (k, 0.0) if axis == "u" else (0.0, k)
     vec = (-SIGMA * hu / np.linalg.norm(pu), -SIGMA * hv * (t1 @ pv) / (pv @ pv), 1.0)
     assert np.allclose(perturbed_normal64(n, e1, e2, q, SIGMA, np.array([hu]), np.array([hv]))[0], (vec[0] * s1 + vec[1] * t1 + n) / np.linalg.norm(vec), atol=1e-12)
-    tbn = scene(quad_xml(normal_xml(0.3, tuple(encode(vec))), tilt), RES, SPP).tables(0)
+    tbn = scene(uv_quad_xml(normal_xml(0.3, tuple(encode(vec))), tilt), RES, SPP).tables(0)
     assert tbn["material_mask"] == 8 and tbh["material_mask"] == 16
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
     a, b = host_colloc_render(tbh, o), host_colloc_render(tbn, o)
     print("height ramp in %s at tilt %g against the type-3 record: rel-L2 %.2e" % (axis, tilt, rel_l2(a, b)))
     assert b.max() > 0 and rel_l2(a, b) <= 2e-6, rel_l2(a, b)
-    flat = host_colloc_render(scene(quad_xml(microfacet_xml(0.3), tilt), RES, SPP).tables(0), o)
+    flat = host_colloc_render(scene(uv_quad_xml(microfacet_xml(0.3), tilt), RES, SPP).tables(0), o)
     assert rel_l2(a, flat) > 1e-3          # (and the ramp shows)
 
 
@@ -107,10 +105,10 @@ def test_limit_flat_height_is_no_map(tilt, case):
     the rounding of Frame(n).to_local(Frame(n).to_world(wi)))."""
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
     kw = {"1x1": {}, "4x4-constant": dict(height=np.full(16, 0.7, np.float32)), "sigma0": dict(height="random", scale=0.0)}[case]
-    tb = scene(quad_xml(height_xml(0.3, height=0.7), tilt), RES, SPP, **kw).tables(0)
+    tb = scene(uv_quad_xml(height_xml(0.3, height=0.7), tilt), RES, SPP, **kw).tables(0)
     assert tb["material_mask"] == 16
     img = host_colloc_render(tb, o)
-    ref = host_colloc_render(scene(quad_xml(microfacet_xml(0.3), tilt), RES, SPP).tables(0), o)
+    ref = host_colloc_render(scene(uv_quad_xml(microfacet_xml(0.3), tilt), RES, SPP).tables(0), o)
     assert ref.max() > 0
     assert rel_l2(img, ref) <= 1e-6, rel_l2(img, ref)
 
@@ -129,7 +127,7 @@ def test_no_map_is_the_record_of_section_14(tilt):
         for m in sc.m_meshes:
             m.bsdf = nb
     tb, tb2 = xml_scene(xml, RES, SPP).tables(0), xml_scene(xml, RES, SPP, prepare=explicit).tables(0)
-    row, _ = microfacet_record(tb2)
+    row, _ = record(tb2, "plain")
     assert row[0] == _abi.BSDF_MICROFACET == 2 and list(row[7:10]) == [0, 1, 1] and list(row[13:16]) == [0, 1, 1] and tb2["material_mask"] == 4
     assert np.array_equal(tb["bsdf_rec"].cpu().numpy(), tb2["bsdf_rec"].cpu().numpy()) and np.array_equal(tb["texels"].cpu().numpy(), tb2["texels"].cpu().numpy())
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
@@ -141,14 +139,14 @@ def test_mixed_scene_dispatches_per_mesh():
     those of the scene that holds that mesh alone, bit for bit."""
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
     kw = dict(textured=True, normal="random", height="random")
-    tbm = scene(mixed_xml(), RES, SPP, **kw).tables(0)
+    tbm = scene(mixed_xml(MIXED_IDS), RES, SPP, **kw).tables(0)
     rec = tbm["bsdf_rec"].cpu().numpy().reshape(-1, _abi.BSDF_STRIDE)
     assert list(rec[:, 0]) == [0, 1, 2, 3, 4] and tbm["material_mask"] == 31
     mixed = host_colloc_render(tbm, o)
     covered = np.zeros(len(mixed), bool)
     solos = {}
     for bid in MIXED_IDS:
-        solo = host_colloc_render(scene(mixed_xml(only=bid), RES, SPP, **kw).tables(0), o)
+        solo = host_colloc_render(scene(mixed_xml(MIXED_IDS, only=bid), RES, SPP, **kw).tables(0), o)
         px = (solo != 0).any(axis=1)
         assert px.sum() >= 4 and not (covered & px).any(), bid          # the five quads cover separate pixels
         assert np.array_equal(mixed[px], solo[px]), bid
@@ -174,9 +172,9 @@ def _all_modes(tb, res, spp, sppe):
 
 def _height_texel_dimg(tb, o):
     """forward mode with a random tangent on the height map's texels and on the scale"""
-    row, off = height_record(tb)
+    row, off = record(tb, "height")
     tan = torch.zeros_like(tb["texels"])
-    n = height_width(row)
+    n = map_words(row, "height")
     tan[off["height"]:off["height"] + n] = torch.rand(n, generator=torch.Generator().manual_seed(3)) - 0.5
     tan[off["scale"]] = 1.0
     return host_colloc_render(tb, o, mode=1, tangents={"texels": tan})[1]
@@ -197,7 +195,7 @@ def test_degenerate_flat_cases(case):
     that the height texels and the scale receive nothing, and the other maps still receive their gradient."""
     res, spp, sppe = 16, 4, 4
     kw = dict(uv="collapse") if case == "coincident-uvs" else dict(extra=_scale_uv(1e13))
-    tb = scene(quad_xml(height_xml(0.3), 30.0), res, spp, sppe, height="random", textured=True, **kw).tables(0)
+    tb = scene(uv_quad_xml(height_xml(0.3), 30.0), res, spp, sppe, height="random", textured=True, **kw).tables(0)
     uvs = tb["tri_uv"].cpu().numpy().astype(np.float64).reshape(tb["num_tris"], -1)[:, :6]
     det = (uvs[:, 2] - uvs[:, 0]) * (uvs[:, 5] - uvs[:, 1]) - (uvs[:, 4] - uvs[:, 0]) * (uvs[:, 3] - uvs[:, 1])
     if case == "coincident-uvs":
@@ -207,10 +205,10 @@ def test_degenerate_flat_cases(case):
         J = np.abs(np.einsum("ij,ij->i", np.cross(T[:, 3:6], T[:, 6:9]), T[:, 18:21]) / det)
         assert (det != 0).all() and np.isfinite(det).all() and (J < 1e-21).all() and (J > 0).all()
     o, img, grads = _all_modes(tb, res, spp, sppe)
-    ref = host_colloc_render(scene(quad_xml(height_xml(0.3), 30.0), res, spp, sppe, height="random", textured=True, drop_height=True, **kw).tables(0), o)
+    ref = host_colloc_render(scene(uv_quad_xml(height_xml(0.3), 30.0), res, spp, sppe, height="random", textured=True, drop_height=True, **kw).tables(0), o)
     assert ref.max() > 0 and rel_l2(img, ref) <= 1e-6
-    row, off = height_record(tb)
-    assert (grads["texels"][off["height"]:off["height"] + height_width(row)] == 0).all() and grads["texels"][off["scale"]] == 0
+    row, off = record(tb, "height")
+    assert (grads["texels"][off["height"]:off["height"] + map_words(row, "height")] == 0).all() and grads["texels"][off["scale"]] == 0
     assert np.abs(grads["texels"][off["kd"]:off["kd"] + 48]).max() > 0
     assert (_height_texel_dimg(tb, o) == 0).all()
 
@@ -222,13 +220,13 @@ def test_degenerate_last_cell():
     (in float64 the wrap gives 1 - 1e-9 and the other end of the cell) at the closed-form bound; the height texels of the last cell, and only those, receive a
     gradient."""
     res, spp, sppe = 16, 4, 4
-    tb = scene(quad_xml(height_xml(0.3), 30.0), res, spp, sppe, uv="mirror", height="random", scale=SIGMA * 1e9, extra=_scale_uv(1e-9)).tables(0)
+    tb = scene(uv_quad_xml(height_xml(0.3), 30.0), res, spp, sppe, uv="mirror", height="random", scale=SIGMA * 1e9, extra=_scale_uv(1e-9)).tables(0)
     o, img, grads = _all_modes(tb, res, spp, sppe)
-    ref = closed_form_image(tb, host_film_samples(tb, o), spp, fp32_uv=True)
-    flat = host_colloc_render(scene(quad_xml(microfacet_xml(0.3), 30.0), res, spp).tables(0), o)
+    ref = closed_form_image(tb, host_film_samples(tb, o), spp, "height", fp32_uv=True)
+    flat = host_colloc_render(scene(uv_quad_xml(microfacet_xml(0.3), 30.0), res, spp).tables(0), o)
     assert ref.max() > 0 and rel_l2(ref, flat) > 1e-3          # the slopes of the last cell show
     assert rel_l2(img, ref) <= max(2e-6, 4 * MEASURED_CLOSED_FORM), rel_l2(img, ref)
-    row, off = height_record(tb)
+    row, off = record(tb, "height")
     g = grads["texels"][off["height"]:off["height"] + 16].reshape(4, 4)
     mask = np.ones((4, 4), bool)
     mask[2:, 2:] = False
@@ -243,11 +241,11 @@ def test_forward_equals_reverse(name):
     smooth-shaded bunny (one tree, planar UVs).  |lhs - rhs| <= 1e-4 x scale, as test_colloc_normal_host.py::test_forward_equals_reverse.  The height map's texel
     range and the scale receive a gradient, and the triangle-row gradient differs from that of the same scene without the map."""
     res, spp, sppe = 16, 4, 4
-    tb = named_scene(name, res, spp, sppe).tables(0)
+    tb = named_scene("height", name, res, spp, sppe).tables(0)
     assert tb["material_mask"] & (1 << _abi.BSDF_MICROFACET_HEIGHT)
     adj = np.random.default_rng(5).random((res * res, 3)).astype(np.float32)
     o = colloc_opts(spp, sppe, rng_offset=(2, 3, 0))
-    row, off = height_record(tb)
+    row, off = record(tb, "height")
     for n in NAMES:
         tan = random_tangents(tb, [n], seed=1)
         img, dimg = host_colloc_render(tb, o, mode=1, tangents=tan)
@@ -259,7 +257,7 @@ def test_forward_equals_reverse(name):
         print("height map forward = reverse, %s %s: lhs %.6e rhs %.6e scale %.3e" % (name, n, lhs, rhs, scale))
         assert abs(lhs - rhs) <= 1e-4 * max(scale, 1e-6), (n, lhs, rhs, scale)
         if n == "texels":
-            for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("height", height_width(row)), ("scale", 1)):
+            for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("height", map_words(row, "height")), ("scale", 1)):
                 assert np.abs(grads["texels"][off[key]:off[key] + width]).max() > 0, key
             # ... and the height texels and the scale alone
             t2 = torch.zeros_like(tan["texels"])
@@ -270,7 +268,7 @@ def test_forward_equals_reverse(name):
             scale = float(np.abs(adj.astype(np.float64) * d2).sum())
             assert scale > 0 and abs(lhs - rhs) <= 1e-4 * scale, (lhs, rhs, scale)
         if n == "tri_info":
-            tb0 = named_scene(name, res, spp, sppe, drop_height=True).tables(0)
+            tb0 = named_scene("height", name, res, spp, sppe, drop_height=True).tables(0)
             assert np.array_equal(tb0["tri_info"].detach().cpu().numpy(), tb["tri_info"].detach().cpu().numpy())
             g0 = host_colloc_rev(tb0, o, adj, want=[n])[1][n]
             assert np.abs(grads[n] - g0).max() > 1e-3 * np.abs(g0).max()
@@ -323,7 +321,7 @@ def test_ad_against_central_differences(which):
         assert tb0["material_mask"] == 4 and np.abs(host_colloc_render(tb0, o, mode=1, tangents=tan)[1]).max() <= 1e-4 * np.abs(ad).max()
     else:
         tb = _big_quad(SPP)[0].tables(0)
-        _, off = height_record(tb)
+        _, off = record(tb, "height")
         i, steps = (off["height"] + 5, (1e-2, 2e-2)) if which == "height-texel" else (off["scale"], (0.15, 0.3))
         base = tb["texels"].detach().clone()
         v0 = float(base[i])
@@ -364,15 +362,15 @@ def test_loader_record_and_mask():
     """<bsdf type="microfacet"> with the children heightMap / height_map (a constant float or a bitmap texture) and heightScale / height_scale; without heightMap: no
     map.  The records and masks tables() emits: type 2 / bit 2 without a map, as before; with one, type 4 / bit 4, the three slots of type 2 unchanged, the scale's
     (offset, 1, 1) in PSDR_SLOT_ALPHA_V and the map's (offset, w, h) in PSDR_SLOT_K.  param_map reaches both, and so does the torch graph."""
-    sc = scene(quad_xml(height_xml(0.3, 0.25, 2.5)), RES, SPP)
-    sc2 = scene(quad_xml(height_xml(0.3, 0.25, 2.5, name="height_map", scale_name="height_scale")), RES, SPP)
-    plain = scene(quad_xml(microfacet_xml(0.3)), RES, SPP)
+    sc = scene(uv_quad_xml(height_xml(0.3, 0.25, 2.5)), RES, SPP)
+    sc2 = scene(uv_quad_xml(height_xml(0.3, 0.25, 2.5, name="height_map", scale_name="height_scale")), RES, SPP)
+    plain = scene(uv_quad_xml(microfacet_xml(0.3)), RES, SPP)
     tb, tb2, tbp = sc.tables(0), sc2.tables(0), plain.tables(0)
     assert tbp["material_mask"] == 4 and tb["material_mask"] == 1 << _abi.BSDF_MICROFACET_HEIGHT == 16
     assert plain.param_map["BSDF[id=m]"].height_map is None
     assert np.array_equal(tb["bsdf_rec"].cpu().numpy(), tb2["bsdf_rec"].cpu().numpy()) and np.array_equal(tb["texels"].cpu().numpy(), tb2["texels"].cpu().numpy())
-    row, off = height_record(tb)
-    rowp, offp = microfacet_record(tbp)
+    row, off = record(tb, "height")
+    rowp, offp = record(tbp, "plain")
     assert row[0] == 4 and rowp[0] == 2 and list(row[1:7]) == list(rowp[1:7]) and list(row[10:13]) == list(rowp[10:13]) and list(rowp[7:10]) == [0, 1, 1] == list(rowp[13:16])
     assert list(row[7:10]) == [off["scale"], 1, 1] and list(row[13:16]) == [off["height"], 1, 1]
     texels = tb["texels"].cpu().numpy()
@@ -382,21 +380,21 @@ def test_loader_record_and_mask():
     b = sc.param_map["BSDF[id=m]"]
     assert isinstance(b, psdr_cuda.MicrofacetBSDF) and isinstance(b.height_map, psdr_cuda.Bitmap1fD) and sc.param_map["BSDF[0]"].height_map is b.height_map
     # the scale without a map: kept on the object, the record stays of type 2
-    only_scale = scene(quad_xml(microfacet_xml(0.3).replace("</bsdf>", '<float name="heightScale" value="3"/></bsdf>')), RES, SPP)
+    only_scale = scene(uv_quad_xml(microfacet_xml(0.3).replace("</bsdf>", '<float name="heightScale" value="3"/></bsdf>')), RES, SPP)
     assert only_scale.tables(0)["material_mask"] == 4 and np.allclose(only_scale.param_map["BSDF[id=m]"].height_scale.tensor().cpu().numpy(), 3.0)
     # a bitmap texture
     bmp = height_xml(0.3).replace('<float name="heightMap" value="0"/>',
                                   '<texture name="heightMap" type="bitmap"><string name="filename" value="./data/textures/test_texture.exr"/></texture>')
     assert "texture" in bmp
-    sb = scene(quad_xml(bmp), RES, SPP)
+    sb = scene(uv_quad_xml(bmp), RES, SPP)
     w, h = sb.param_map["BSDF[id=m]"].height_map.resolution
     assert w > 1 and h > 1
-    rowb, _ = height_record(sb.tables(0))
+    rowb, _ = record(sb.tables(0), "height")
     assert list(rowb[14:16]) == [w, h]
     # both maps in one element
     with pytest.raises(RuntimeError, match=NOT_BOTH):
-        scene(quad_xml(normal_xml(0.3).replace("</bsdf>", '<float name="heightMap" value="0"/></bsdf>')), RES, SPP)
-    late = scene(quad_xml(height_xml(0.3)), RES, SPP)
+        scene(uv_quad_xml(normal_xml(0.3).replace("</bsdf>", '<float name="heightMap" value="0"/></bsdf>')), RES, SPP)
+    late = scene(uv_quad_xml(height_xml(0.3)), RES, SPP)
     late.param_map["BSDF[id=m]"].normal_map = psdr_cuda.Bitmap3fD((0.5, 0.5, 1.0))
     with pytest.raises(RuntimeError, match=NOT_BOTH):
         late.configure()
@@ -414,18 +412,18 @@ def test_refusals():
     """DirectIntegrator and PathTracer keep raising the MicrofacetBSDF message for a height-mapped record; a mesh without texture coordinates under a height map
     raises the new message before any native call, from every entry of the CollocatedIntegrator -- bunny_light as it is: bunny_low.obj has no texture
     coordinates."""
-    sc = scene(quad_xml(height_xml(0.3)), RES, SPP, height="random")
+    sc = scene(uv_quad_xml(height_xml(0.3)), RES, SPP, height="random")
     direct, path = psdr_cuda.DirectIntegrator(1, 1), psdr_cuda.PathTracer(3, True)
     for call in (lambda: direct.renderC(sc), lambda: direct.renderD(sc), lambda: direct.preprocess_secondary_edges(sc, 0, [2, 2, 2, 1]),
                  lambda: path.renderC(sc), lambda: path.renderD(sc), lambda: path.preprocess_path_secondary_edges(sc, 0, [2, 2, 2, 1])):
         with pytest.raises(RuntimeError, match=MESSAGE):
             call()
     psdr_cuda.CollocatedIntegrator(1.0)._check_bsdfs(sc)
-    bare = scene(plain_bunny_xml().replace("</bsdf>", '<float name="heightMap" value="0"/></bsdf>', 1), RES, SPP)
+    bare = scene(bunny_xml("plain").replace("</bsdf>", '<float name="heightMap" value="0"/></bsdf>', 1), RES, SPP)
     assert bare.tables(0)["tri_uv"] is None and bare.tables(0)["material_mask"] & 16
     colloc = psdr_cuda.CollocatedIntegrator(1.0)
     for call in (lambda: colloc.renderC(bare), lambda: colloc.renderD(bare)):
-        with pytest.raises(RuntimeError, match=NEEDS_UV):
+        with pytest.raises(RuntimeError, match=KINDS["height"].needs_uv):
             call()
     with pytest.raises(RuntimeError, match=MESSAGE):          # the older message first, as the C ABI orders them
         direct.renderC(bare)
@@ -433,19 +431,11 @@ def test_refusals():
 
 # ---------------------------------------------------------------- 8. the same host functions under the sanitizers
 def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
-    """tests/hostcheck/colloc_height_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with
-    -fsanitize=address,undefined for the host: render, forward and reverse on the tiny scene of the five record types; it must end clean and report what the
+    """tests/hostcheck/colloc_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with
+    -fsanitize=address,undefined for the host (hostlibs.san_program) and asked for a record of type BSDF_MICROFACET_HEIGHT:
+    render, forward and reverse on the tiny scene of the five record types; it must end clean and report what the
     library reports.  It refuses tables without a type-4 record."""
-    exe, src = os.path.join(HC_DIR, "colloc_height_san"), os.path.join(HC_DIR, "colloc_height_san.cpp")
-    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in HC_DEPS + [src]):
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-pthread", src, "-o", exe]
-        san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-        r = subprocess.run(cmd + san, capture_output=True, text=True)
-        if r.returncode != 0 and ("libclang_rt" in r.stderr or "sanitizer" in r.stderr.lower()):
-            # no host sanitizer runtime beside this compiler: the program still runs the same functions over the same tables, without the instrumentation
-            print("colloc_height_san: built WITHOUT the sanitizers, the compiler's host runtime for them is missing:\n" + r.stderr[-800:])
-            r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, "colloc_height_san does not compile:\n" + r.stderr[-3000:]
+    exe = san_program("colloc_san", HC_DEPS)
     res, spp, sppe = 8, 2, 2
     o = colloc_opts(spp, sppe, rng_offset=(1, 2, 0))
     adj = np.random.default_rng(4).random((res * res, 3)).astype(np.float32)
@@ -456,10 +446,10 @@ def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
         tbc, desc, keep = cpu_desc(tb)
         path = str(tmp_path / name)
         write_tables_file(path, desc, keep, o, *[tan[n].detach().cpu().numpy().astype(np.float32) for n in ("tri_info", "texels", "prim_edge")], adj)
-        return tan, subprocess.run([exe, path], capture_output=True, text=True, env=env, timeout=600)
-    _, r = run(scene(mixed_xml(only="n"), res, spp, sppe, textured=True, normal="random", uv="rot37", drop_height=True).tables(0), "no_height.bin")
+        return tan, subprocess.run([exe, path, str(_abi.BSDF_MICROFACET_HEIGHT)], capture_output=True, text=True, env=env, timeout=600)
+    _, r = run(scene(mixed_xml(MIXED_IDS, only="n"), res, spp, sppe, textured=True, normal="random", uv="rot37", drop_height=True).tables(0), "no_height.bin")
     assert r.returncode == 2 and "no height-mapped" in r.stderr, (r.returncode, r.stderr[-1000:])
-    tb = scene(mixed_xml(), res, spp, sppe, textured=True, normal="random", height="random", uv="rot37").tables(0)
+    tb = scene(mixed_xml(MIXED_IDS), res, spp, sppe, textured=True, normal="random", height="random", uv="rot37").tables(0)
     tan, r = run(tb, "tables.bin")
     assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-3000:])
     got = [float(x) for x in r.stdout.split()]

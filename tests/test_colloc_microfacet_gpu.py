@@ -10,16 +10,17 @@ import torch
 import enoki as ek
 import psdr_cuda
 from collocated_helpers import colloc_opts, host_colloc_render, host_colloc_rev
-from colloc_microfacet_helpers import MESSAGE, bunny_xml, microfacet_record, microfacet_xml, mixed_xml, room_xml, scene, uv_quad_xml
+from colloc_microfacet_helpers import MESSAGE, bunny_xml, microfacet_xml, mixed_xml, record, room_xml, scene, uv_quad_xml
 from enoki.cuda_autodiff import Float32 as FloatD, Vector3f as Vector3fD
 from helpers import GpuScene, dot_tables, isolated_pixels_unbiased, random_tangents, rel_l2
 from psdr_cuda import _abi
 
 pytestmark = pytest.mark.gpu
+MIXED_IDS = ("d", "c", "m")          # the quads of mixed_xml: record types 0 .. 2
 
 
 def _xml(name):
-    return {"quad": uv_quad_xml(microfacet_xml(0.3), 30.0), "room": room_xml(), "bunny": bunny_xml(), "mixed": mixed_xml()}[name]
+    return {"quad": uv_quad_xml(microfacet_xml(0.3), 30.0), "room": room_xml("plain"), "bunny": bunny_xml("plain"), "mixed": mixed_xml(MIXED_IDS)}[name]
 
 
 @pytest.mark.parametrize("name,tree", [("quad", False), ("room", False), ("bunny", True), ("mixed", False)])
@@ -45,7 +46,7 @@ def test_render_c_matches_the_harness(name, tree):
 
 def _map_sets(tb):
     """one tangent set per map of the MicrofacetBSDF: random tangents on the 4 x 4 kd, F0 and roughness texels, zero elsewhere"""
-    _, off = microfacet_record(tb)
+    _, off = record(tb, "plain")
     rnd = random_tangents(tb, ["texels"], seed=2)["texels"]
     sets = []
     for key, width in (("kd", 48), ("f0", 48), ("roughness", 16)):
@@ -96,7 +97,7 @@ def test_reverse_equals_forward(name):
     names = ["tri_info", "texels", "cam_to_world", "prim_edge"]
     img_r, grads = g.render_d_rev(o, adj, want=names)
     _, host_grads = host_colloc_rev(tb, o, adj, want=names)
-    _, off = microfacet_record(tb)
+    _, off = record(tb, "plain")
     for key, width in (("kd", 48), ("f0", 48), ("roughness", 16)):
         assert np.abs(grads["texels"][off[key]:off[key] + width]).max() > 0, key
     for n in names:
@@ -136,7 +137,7 @@ def test_python_surface():
     want_I = (adj.astype(np.float64) * unit).sum(axis=0)
     assert np.abs(want_I).min() > 0 and np.allclose(gI, want_I, rtol=1e-4), (gI, want_I)
     _, cg = g.render_d_rev(o, adj * np.array(inten, np.float32), want=["texels"])
-    _, off = microfacet_record(tb)
+    _, off = record(tb, "plain")
     for m, key in zip(maps, ("kd", "f0", "roughness")):
         got = ek.gradient(m).numpy().reshape(-1)
         want = cg["texels"][off[key]:off[key] + got.size]

@@ -9,15 +9,16 @@ import numpy as np
 import pytest
 
 import psdr_cuda
-from collocated_helpers import HC_DEPS, HC_DIR, ROUGH, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, xml_scene
-from colloc_microfacet_helpers import (F0, KD, MESSAGE, bunny_xml, closed_form_image, diffuse_xml, microfacet_record, microfacet_xml, mixed_xml, room_xml,
+from collocated_helpers import HC_DEPS, ROUGH, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, xml_scene
+from colloc_microfacet_helpers import (F0, KD, MESSAGE, bunny_xml, closed_form_image, diffuse_xml, microfacet_xml, mixed_xml, record, room_xml,
                                        scene, uv_quad_xml)
 from helpers import dot_tables, host_render, random_tangents, rel_l2
-from hostlibs import cpu_desc, write_tables_file
+from hostlibs import cpu_desc, san_program, write_tables_file
 from psdr_cuda import _abi
 
 RES, SPP = 16, 4
 TILTS, ROUGHNESS = (0.0, 30.0, 70.0), (0.3, 0.6)
+MIXED_IDS = ("d", "c", "m")          # the quads of mixed_xml: record types 0 .. 2
 
 
 # ---------------------------------------------------------------- 1. closed form
@@ -33,7 +34,7 @@ def test_closed_form(tilt, r, textured):
     tb = sc.tables(0)
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
     img = host_colloc_render(tb, o)
-    ref = closed_form_image(tb, host_film_samples(tb, o), SPP)
+    ref = closed_form_image(tb, host_film_samples(tb, o), SPP, "plain")
     assert (ref > 0).any() and (ref == 0).any()          # the quad and the background are both seen
     e = rel_l2(img, ref)
     print("microfacet closed form tilt %g r %g %s: rel-L2 %.2e" % (tilt, r, "4x4" if textured else "1x1", e))
@@ -84,7 +85,7 @@ def test_limit_no_diffuse_is_the_rough_conductor(tilt, r):
 
 # ---------------------------------------------------------------- 3. forward = reverse
 def _fwd_rev_scene(name, res, spp, sppe):
-    xml = {"quad": uv_quad_xml(microfacet_xml(0.3), 30.0), "room": room_xml(), "bunny": bunny_xml()}[name]
+    xml = {"quad": uv_quad_xml(microfacet_xml(0.3), 30.0), "room": room_xml("plain"), "bunny": bunny_xml("plain")}[name]
     return scene(xml, res, spp, sppe, textured=True)
 
 
@@ -98,7 +99,7 @@ def test_forward_equals_reverse(name):
     assert tb["material_mask"] & (1 << _abi.BSDF_MICROFACET)
     adj = np.random.default_rng(5).random((res * res, 3)).astype(np.float32)
     o = colloc_opts(spp, sppe, rng_offset=(2, 3, 0))
-    _, off = microfacet_record(tb)
+    _, off = record(tb, "plain")
     for n in ("texels", "tri_info", "cam_to_world", "prim_edge"):
         tan = random_tangents(tb, [n], seed=1)
         img, dimg = host_colloc_render(tb, o, mode=1, tangents=tan)
@@ -123,7 +124,7 @@ def test_ad_against_central_differences(which):
     2.572e-8.  kd and F0 enter linearly: their floor is fp32 rounding over the step; the roughness floor is the differences' third-order term."""
     tb = scene(uv_quad_xml(microfacet_xml(0.3), 30.0), RES, SPP, textured=True).tables(0)
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
-    _, off = microfacet_record(tb)
+    _, off = record(tb, "plain")
     i = off[which] + (5 if which == "roughness" else 3 * 5 + 1)          # texel (1, 1), an inner one; the green channel
     base = tb["texels"].detach().clone()
     v0 = float(base[i])
@@ -148,11 +149,11 @@ def test_ad_against_central_differences(which):
 def test_mixed_scene_dispatches_per_mesh():
     """A diffuse, a rough-conductor and a microfacet quad in one scene: each mesh's pixels equal those of the scene that holds that mesh alone, bit for bit."""
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
-    mixed = host_colloc_render(scene(mixed_xml(), RES, SPP, textured=True).tables(0), o)
+    mixed = host_colloc_render(scene(mixed_xml(MIXED_IDS), RES, SPP, textured=True).tables(0), o)
     covered = np.zeros(len(mixed), bool)
     solos = {}
     for bid in ("d", "c", "m"):
-        solo = host_colloc_render(scene(mixed_xml(only=bid), RES, SPP, textured=True).tables(0), o)
+        solo = host_colloc_render(scene(mixed_xml(MIXED_IDS, only=bid), RES, SPP, textured=True).tables(0), o)
         px = (solo != 0).any(axis=1)
         assert px.sum() >= 4 and not (covered & px).any(), bid          # the three quads cover separate pixels
         assert np.array_equal(mixed[px], solo[px]), bid
@@ -168,7 +169,7 @@ def test_zero_roughness_texel_stays_finite():
     it the lobe is a narrow, finite spike): image, derivative image and every gradient table stay finite."""
     res, spp, sppe = 16, 4, 4
     tb = scene(uv_quad_xml(microfacet_xml(0.3), 0.0), res, spp, sppe, textured=True, zero_roughness_texel=5).tables(0)
-    _, off = microfacet_record(tb)
+    _, off = record(tb, "plain")
     assert float(tb["texels"][off["roughness"] + 5]) == 0.0
     o = colloc_opts(spp, sppe, rng_offset=(2, 3, 0))
     names = ["texels", "tri_info", "cam_to_world", "prim_edge"]
@@ -210,7 +211,7 @@ def test_loader_record_and_mask():
     sc2 = scene(uv_quad_xml(snake), RES, SPP)
     tb, tb2 = sc.tables(0), sc2.tables(0)
     assert tb["material_mask"] == 1 << _abi.BSDF_MICROFACET == 4
-    row, off = microfacet_record(tb)
+    row, off = record(tb, "plain")
     assert np.array_equal(tb["bsdf_rec"].cpu().numpy(), tb2["bsdf_rec"].cpu().numpy()) and np.array_equal(tb["texels"].cpu().numpy(), tb2["texels"].cpu().numpy())
     tex = tb["texels"].cpu().numpy()
     assert np.allclose(tex[off["kd"]:off["kd"] + 3], KD) and np.allclose(tex[off["f0"]:off["f0"] + 3], F0) and np.isclose(tex[off["roughness"]], 0.3)
@@ -245,20 +246,12 @@ def test_sampling_integrators_refuse_the_scene():
 
 # ---------------------------------------------------------------- 8. the same host functions under the sanitizers
 def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
-    """tests/hostcheck/colloc_microfacet_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with
-    -fsanitize=address,undefined for the host: render, forward and reverse on the tiny mixed scene; it must end clean and report what the library reports."""
-    exe, src = os.path.join(HC_DIR, "colloc_microfacet_san"), os.path.join(HC_DIR, "colloc_microfacet_san.cpp")
-    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in HC_DEPS + [src]):
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-pthread", src, "-o", exe]
-        san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-        r = subprocess.run(cmd + san, capture_output=True, text=True)
-        if r.returncode != 0 and ("libclang_rt" in r.stderr or "sanitizer" in r.stderr.lower()):
-            # no host sanitizer runtime beside this compiler: the program still runs the same functions over the same tables, without the instrumentation
-            print("colloc_microfacet_san: built WITHOUT the sanitizers, the compiler's host runtime for them is missing:\n" + r.stderr[-800:])
-            r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, "colloc_microfacet_san does not compile:\n" + r.stderr[-3000:]
+    """tests/hostcheck/colloc_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with
+    -fsanitize=address,undefined for the host (hostlibs.san_program) and asked for a record of type BSDF_MICROFACET:
+    render, forward and reverse on the tiny mixed scene; it must end clean and report what the library reports."""
+    exe = san_program("colloc_san", HC_DEPS)
     res, spp, sppe = 8, 2, 2
-    tb = scene(mixed_xml(), res, spp, sppe, textured=True).tables(0)
+    tb = scene(mixed_xml(MIXED_IDS), res, spp, sppe, textured=True).tables(0)
     o = colloc_opts(spp, sppe, rng_offset=(1, 2, 0))
     tan = random_tangents(tb, ["tri_info", "texels", "prim_edge"], seed=3)
     adj = np.random.default_rng(4).random((res * res, 3)).astype(np.float32)
@@ -266,7 +259,7 @@ def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
     path = str(tmp_path / "tables.bin")
     write_tables_file(path, desc, keep, o, *[tan[n].detach().cpu().numpy().astype(np.float32) for n in ("tri_info", "texels", "prim_edge")], adj)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, path], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run([exe, path, str(_abi.BSDF_MICROFACET)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-3000:])
     got = [float(x) for x in r.stdout.split()]
     img, dimg = host_colloc_render(tb, o, mode=1, tangents=tan, nthreads=2)

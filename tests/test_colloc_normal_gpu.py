@@ -8,24 +8,24 @@ import torch
 import enoki as ek
 import psdr_cuda
 from collocated_helpers import colloc_opts, host_colloc_render, host_colloc_rev
-from colloc_microfacet_helpers import MESSAGE
-from colloc_normal_helpers import (NEEDS_UV, RECOVERY_INTENSITY, RECOVERY_LR, RECOVERY_STEPS, RECOVERY_TILTS, lean_texel, mixed_xml, named_scene, normal_record,
-                                   normal_width, normal_xml, quad_xml, recovery_errors, recovery_start, recovery_truth, recovery_xml, scene)
+from colloc_microfacet_helpers import KINDS, MESSAGE, RECOVERY, lean_texel, map_words, mixed_xml, named_scene, normal_xml, record, scene, uv_quad_xml
 from enoki.cuda_autodiff import Float32 as FloatD, Vector3f as Vector3fD
 from helpers import GpuScene, dot_tables, isolated_pixels_unbiased, random_tangents, rel_l2
 from psdr_cuda import _abi
 
 pytestmark = pytest.mark.gpu
+MIXED_IDS = ("d", "c", "m", "n")          # the quads of mixed_xml: record types 0 .. 3
+R = RECOVERY["normal"]
 
 
 def _scene(name, res, spp, sppe=0):
     """the scene forms of the host file's forward = reverse test (rotated-UV quad, room without a tree, bunny with one), the mirrored-UV quad and the scene of the
     four record types; 4 x 4 maps on every slot"""
     if name == "mirror":
-        return scene(quad_xml(normal_xml(0.3), 30.0), res, spp, sppe, uv="mirror", normal="random", textured=True)
+        return scene(uv_quad_xml(normal_xml(0.3), 30.0), res, spp, sppe, uv="mirror", normal="random", textured=True)
     if name == "mixed":
-        return scene(mixed_xml(), res, spp, sppe, uv="rot37", normal="random", textured=True)
-    return named_scene(name, res, spp, sppe)
+        return scene(mixed_xml(MIXED_IDS), res, spp, sppe, uv="rot37", normal="random", textured=True)
+    return named_scene("normal", name, res, spp, sppe)
 
 
 @pytest.mark.parametrize("name,tree", [("quad", False), ("room", False), ("bunny", True), ("mirror", False)])
@@ -51,12 +51,12 @@ def test_render_c_matches_the_harness(name, tree):
 
 def _normal_sets(tb):
     """three tangent sets on the normal map's texels: random on the x, the y and the z channel of every texel"""
-    row, off = normal_record(tb)
+    row, off = record(tb, "normal")
     rnd = random_tangents(tb, ["texels"], seed=2)["texels"]
     sets = []
     for ch in range(3):
         t = torch.zeros_like(rnd)
-        idx = torch.arange(off["normal"] + ch, off["normal"] + normal_width(row), 3)
+        idx = torch.arange(off["normal"] + ch, off["normal"] + map_words(row, "normal"), 3)
         t[idx] = rnd[idx]
         sets.append({"texels": t})
     return sets
@@ -103,8 +103,8 @@ def test_reverse_equals_forward(name):
     names = ["tri_info", "texels", "cam_to_world", "prim_edge"]
     img_r, grads = g.render_d_rev(o, adj, want=names)
     _, host_grads = host_colloc_rev(tb, o, adj, want=names)
-    row, off = normal_record(tb)
-    for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("normal", normal_width(row))):
+    row, off = record(tb, "normal")
+    for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("normal", map_words(row, "normal"))):
         assert np.abs(grads["texels"][off[key]:off[key] + width]).max() > 0, key
     for n in names:
         tan = random_tangents(tb, [n], seed=1)
@@ -136,7 +136,7 @@ def test_python_surface():
     tb = sc.tables(0)
     g = GpuScene(tb)
     _, cg = g.render_d_rev(colloc_opts(4, 4), adj * np.array(inten, np.float32), want=["texels"])
-    _, off = normal_record(tb)
+    _, off = record(tb, "normal")
     for m, key in zip(maps, ("kd", "f0", "roughness", "normal")):
         got = ek.gradient(m).numpy().reshape(-1)
         want = cg["texels"][off[key]:off[key] + got.size]
@@ -161,7 +161,7 @@ def test_error_returns():
     build.  A type-3 record in tables whose tri_uv is NULL: "a normal map needs texture coordinates" from the three render entry points, no silent fallback.  The
     handle stays intact: with the table back, the CollocatedIntegrator renders what the harness renders."""
     light = '<ref id="m"/><emitter type="area"><rgb name="radiance" value="5, 5, 5"/></emitter>'          # (an emitter, so that "No Emitter!" is not the answer)
-    sc = scene(quad_xml(normal_xml(0.3, lean_texel()), 30.0).replace('<ref id="m"/>', light), 16, 4, 4)
+    sc = scene(uv_quad_xml(normal_xml(0.3, lean_texel()), 30.0).replace('<ref id="m"/>', light), 16, 4, 4)
     tb = sc.tables(0)
     assert tb["num_emitters"] == 1 and tb["material_mask"] == 8
     g = GpuScene(tb)
@@ -179,7 +179,7 @@ def test_error_returns():
     gb = GpuScene(bare)
     o = colloc_opts(4, 4)
     for call in (lambda: gb.render_c(o), lambda: gb.render_d_fwd(o, [tan]), lambda: gb.render_d_rev(o, adj, want=["texels"])):
-        with pytest.raises(RuntimeError, match=NEEDS_UV):
+        with pytest.raises(RuntimeError, match=KINDS["normal"].needs_uv):
             call()
     with pytest.raises(RuntimeError, match=MESSAGE):          # the older message first
         gb.render_c(_abi.make_opts(integrator=_abi.INTEGRATOR_DIRECT, max_depth=1, spp=4))
@@ -191,7 +191,7 @@ def _recovery_scene(tilt, spp, kd, nm):
         b = sc.m_bsdfs[0]
         b.diffuse_reflectance.resolution = b.normal_map.resolution = (4, 4)
         b.diffuse_reflectance.data, b.normal_map.data = kd, nm
-    return scene(recovery_xml(tilt), 32, spp, 0, extra=maps)
+    return scene(R.xml(tilt), 32, spp, 0, extra=maps)
 
 
 def test_recover_albedo_and_normal_maps():
@@ -199,20 +199,20 @@ def test_recover_albedo_and_normal_maps():
     normal's component along it open), a 4 x 4 kd map started at 0.5 and a 4 x 4 normal map started flat, roughness and F0 known; the target rendered at 64 spp;
     40 Adam steps on both maps.  Condition: the mean kd texel error and the mean angular error of the normals both end below half of their start.
     The step length (0.05) comes from the same loop over the host harness: kd 0.1507 -> 0.0217, normals 17.04 -> 3.40 degrees (at 0.02: 0.0214, 3.70)."""
-    kd_true, n_true = recovery_truth()
-    integ = psdr_cuda.CollocatedIntegrator(RECOVERY_INTENSITY)          # the quad is 1000 away: pixel values of order 0.1
+    kd_true, n_true = R.truth()
+    integ = psdr_cuda.CollocatedIntegrator(R.intensity)          # the quad is 1000 away: pixel values of order 0.1
     targets = []
-    for tilt in RECOVERY_TILTS:
+    for tilt in R.tilts:
         ref = _recovery_scene(tilt, 64, Vector3fD(torch.from_numpy(kd_true)), Vector3fD(torch.from_numpy(n_true)))
         targets.append(integ.renderC(ref).torch().clone())
-    kd0, nm0 = recovery_start()
+    kd0, nm0 = R.start()
     kd, nm = Vector3fD(torch.from_numpy(kd0)), Vector3fD(torch.from_numpy(nm0))
     ek.set_requires_gradient(kd)
     ek.set_requires_gradient(nm)
-    scenes = [_recovery_scene(tilt, 4, kd, nm) for tilt in RECOVERY_TILTS]
-    start = recovery_errors(kd.numpy(), nm.numpy())
-    opt = torch.optim.Adam([kd.t, nm.t], lr=RECOVERY_LR)
-    for it in range(RECOVERY_STEPS):
+    scenes = [_recovery_scene(tilt, 4, kd, nm) for tilt in R.tilts]
+    start = R.errors(kd.numpy(), nm.numpy())
+    opt = torch.optim.Adam([kd.t, nm.t], lr=R.lr)
+    for it in range(R.steps):
         opt.zero_grad()
         for sc, target in zip(scenes, targets):
             sc.configure()
@@ -221,6 +221,6 @@ def test_recover_albedo_and_normal_maps():
         opt.step()
         kd.t.data.clamp_(0.01, 0.99)
         nm.t.data.clamp_(0.0, 1.0)
-    end = recovery_errors(kd.numpy(), nm.numpy())
+    end = R.errors(kd.numpy(), nm.numpy())
     print("normal map recovery: mean kd texel error %.4f -> %.4f, mean angular error of the normals %.2f -> %.2f degrees" % (start[0], end[0], start[1], end[1]))
     assert end[0] < 0.5 * start[0] and end[1] < 0.5 * start[1], (start, end)

@@ -11,20 +11,18 @@ import torch
 
 import enoki as ek
 import psdr_cuda
-from collocated_helpers import HC_DEPS, HC_DIR, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, xml_scene
-from colloc_microfacet_helpers import MESSAGE, closed_form_image as closed_form_flat, microfacet_record, microfacet_xml, uv_quad_xml
-from colloc_microfacet_helpers import bunny_xml as plain_bunny_xml
-from colloc_normal_helpers import (FLAT, MIXED_IDS, NEEDS_UV, closed_form_image, encode, lean_texel, mixed_xml, named_scene, normal_record, normal_width, normal_xml,
-                                   quad, quad_xml, random_normal_texels, scene)
-from collocated_helpers import _HEAD
+from collocated_helpers import HC_DEPS, _HEAD, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, xml_scene
+from colloc_microfacet_helpers import (FLAT, KINDS, MESSAGE, bunny_xml, closed_form_image, encode, lean_texel, map_words, microfacet_xml, mixed_xml, named_scene, normal_xml,
+                                       quad, random_normal_texels, record, scene, uv_quad_xml)
 from enoki.cuda_autodiff import Float32 as FloatD
 from helpers import dot_tables, random_tangents, rel_l2, tangents_wrt
-from hostlibs import cpu_desc, write_tables_file
+from hostlibs import cpu_desc, san_program, write_tables_file
 from psdr_cuda import _abi
 
 RES, SPP = 16, 4
 TILTS, ROUGHNESS = (0.0, 30.0, 70.0), (0.3, 0.6)
 NAMES = ["texels", "tri_info", "cam_to_world", "prim_edge"]
+MIXED_IDS = ("d", "c", "m", "n")          # the quads of mixed_xml: record types 0 .. 3
 
 
 # ---------------------------------------------------------------- 1. closed form
@@ -45,14 +43,14 @@ def test_closed_form(tilt, r, uv, case):
     with the normal leaning up to 50 degrees on a quad seen at 70, samples reach wi'.z -> 0, where the specular lobe's 1 / (4 wi'.z) amplifies the fp32 rounding
     of wi'.z."""
     if case == "lean20":
-        sc = scene(quad_xml(normal_xml(r, lean_texel(20.0)), tilt), RES, SPP, uv=uv)
+        sc = scene(uv_quad_xml(normal_xml(r, lean_texel(20.0)), tilt), RES, SPP, uv=uv)
     else:
-        sc = scene(quad_xml(normal_xml(r), tilt), RES, SPP, uv=uv, normal="random")
+        sc = scene(uv_quad_xml(normal_xml(r), tilt), RES, SPP, uv=uv, normal="random")
     tb = sc.tables(0)
     assert tb["material_mask"] == 1 << _abi.BSDF_MICROFACET_NORMAL
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
     img = host_colloc_render(tb, o)
-    ref = closed_form_image(tb, host_film_samples(tb, o), SPP)
+    ref = closed_form_image(tb, host_film_samples(tb, o), SPP, "normal")
     assert (ref > 0).any() and (ref == 0).any()          # the quad and the background are both seen
     e = rel_l2(img, ref)
     print("normal map closed form tilt %g r %g %s %s: rel-L2 %.2e" % (tilt, r, uv, case, e))
@@ -62,7 +60,7 @@ def test_closed_form(tilt, r, uv, case):
 def test_closed_form_tells_the_tangent():
     """the closed form itself tells the frames apart: the lean-20 image with plain UVs differs from the one with UVs turned by 37 degrees by more than 1e-2"""
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
-    a, b = (host_colloc_render(scene(quad_xml(normal_xml(0.3, lean_texel(20.0)), 30.0), RES, SPP, uv=uv).tables(0), o) for uv in (None, "rot37"))
+    a, b = (host_colloc_render(scene(uv_quad_xml(normal_xml(0.3, lean_texel(20.0)), 30.0), RES, SPP, uv=uv).tables(0), o) for uv in (None, "rot37"))
     assert rel_l2(a, b) > 1e-2
 
 
@@ -71,8 +69,8 @@ def test_closed_form_tells_the_tangent():
 def test_limit_flat_map_is_no_map(tilt):
     """A 1 x 1 map (0.5, 0.5, 1) equals normal_map = None to 1e-6 rel-L2 (n' = n; what differs is the rounding of Frame(n).to_local(Frame(n).to_world(wi)))."""
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
-    img = host_colloc_render(scene(quad_xml(normal_xml(0.3, FLAT), tilt), RES, SPP).tables(0), o)
-    ref = host_colloc_render(scene(quad_xml(microfacet_xml(0.3), tilt), RES, SPP).tables(0), o)
+    img = host_colloc_render(scene(uv_quad_xml(normal_xml(0.3, FLAT), tilt), RES, SPP).tables(0), o)
+    ref = host_colloc_render(scene(uv_quad_xml(microfacet_xml(0.3), tilt), RES, SPP).tables(0), o)
     assert ref.max() > 0
     assert rel_l2(img, ref) <= 1e-6, rel_l2(img, ref)
 
@@ -92,27 +90,27 @@ def test_no_map_is_the_record_of_section_14(tilt, r):
         for m in sc.m_meshes:
             m.bsdf = nb
     tb, tb2 = xml_scene(xml, RES, SPP).tables(0), xml_scene(xml, RES, SPP, prepare=explicit).tables(0)
-    row, _ = microfacet_record(tb2)
+    row, _ = record(tb2, "plain")
     assert row[0] == _abi.BSDF_MICROFACET == 2 and list(row[1 + 3 * _abi.SLOT_K:4 + 3 * _abi.SLOT_K]) == [0, 1, 1] and tb2["material_mask"] == 4
     assert np.array_equal(tb["bsdf_rec"].cpu().numpy(), tb2["bsdf_rec"].cpu().numpy()) and np.array_equal(tb["texels"].cpu().numpy(), tb2["texels"].cpu().numpy())
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
     img, img2 = host_colloc_render(tb, o), host_colloc_render(tb2, o)
     assert np.array_equal(img, img2)
-    assert rel_l2(img2, closed_form_flat(tb2, host_film_samples(tb2, o), SPP)) <= 2e-6
+    assert rel_l2(img2, closed_form_image(tb2, host_film_samples(tb2, o), SPP, "plain")) <= 2e-6
 
 
 def test_mixed_scene_dispatches_per_mesh():
     """A diffuse, a rough-conductor, a microfacet and a normal-mapped microfacet quad (record types 0, 1, 2, 3) in one scene: each mesh's pixels equal those of the
     scene that holds that mesh alone, bit for bit."""
     o = colloc_opts(SPP, rng_offset=(5, 0, 0))
-    tbm = scene(mixed_xml(), RES, SPP, textured=True).tables(0)
+    tbm = scene(mixed_xml(MIXED_IDS), RES, SPP, textured=True).tables(0)
     rec = tbm["bsdf_rec"].cpu().numpy().reshape(-1, _abi.BSDF_STRIDE)
     assert list(rec[:, 0]) == [0, 1, 2, 3] and tbm["material_mask"] == 15
     mixed = host_colloc_render(tbm, o)
     covered = np.zeros(len(mixed), bool)
     solos = {}
     for bid in MIXED_IDS:
-        solo = host_colloc_render(scene(mixed_xml(only=bid), RES, SPP, textured=True).tables(0), o)
+        solo = host_colloc_render(scene(mixed_xml(MIXED_IDS, only=bid), RES, SPP, textured=True).tables(0), o)
         px = (solo != 0).any(axis=1)
         assert px.sum() >= 4 and not (covered & px).any(), bid          # the four quads cover separate pixels
         assert np.array_equal(mixed[px], solo[px]), bid
@@ -138,9 +136,9 @@ def _all_modes(tb, res, spp, sppe):
 
 def _normal_texel_dimg(tb, o):
     """forward mode with a random tangent on the normal map's texels alone"""
-    row, off = normal_record(tb)
+    row, off = record(tb, "normal")
     tan = torch.zeros_like(tb["texels"])
-    n = normal_width(row)
+    n = map_words(row, "normal")
     tan[off["normal"]:off["normal"] + n] = torch.rand(n, generator=torch.Generator().manual_seed(3)) - 0.5
     return host_colloc_render(tb, o, mode=1, tangents={"texels": tan})[1]
 
@@ -149,14 +147,14 @@ def test_degenerate_coincident_uvs():
     """A quad whose UVs all coincide (det = 0): n' = n, so the image is that of the record without a map (1e-6 rel-L2, as the flat-map limit) whatever the map says;
     forward and reverse mode agree that the normal texels receive nothing, and the other maps still receive their gradient."""
     res, spp, sppe = 16, 4, 4
-    tb = scene(quad_xml(normal_xml(0.3), 30.0), res, spp, sppe, uv="collapse", normal="random", textured=True).tables(0)
+    tb = scene(uv_quad_xml(normal_xml(0.3), 30.0), res, spp, sppe, uv="collapse", normal="random", textured=True).tables(0)
     uvs = tb["tri_uv"].cpu().numpy().reshape(tb["num_tris"], -1)[:, :6]
     assert (uvs[:, 0:2] == uvs[:, 2:4]).all() and (uvs[:, 0:2] == uvs[:, 4:6]).all()
     o, img, grads = _all_modes(tb, res, spp, sppe)
-    ref = host_colloc_render(scene(quad_xml(normal_xml(0.3), 30.0), res, spp, sppe, uv="collapse", normal="random", textured=True, drop_normal=True).tables(0), o)
+    ref = host_colloc_render(scene(uv_quad_xml(normal_xml(0.3), 30.0), res, spp, sppe, uv="collapse", normal="random", textured=True, drop_normal=True).tables(0), o)
     assert ref.max() > 0 and rel_l2(img, ref) <= 1e-6
-    row, off = normal_record(tb)
-    assert (grads["texels"][off["normal"]:off["normal"] + normal_width(row)] == 0).all()
+    row, off = record(tb, "normal")
+    assert (grads["texels"][off["normal"]:off["normal"] + map_words(row, "normal")] == 0).all()
     assert np.abs(grads["texels"][off["kd"]:off["kd"] + 48]).max() > 0
     assert (_normal_texel_dimg(tb, o) == 0).all()
 
@@ -165,14 +163,14 @@ def test_degenerate_zero_vector_texel():
     """A texel that decodes to v = 0 (c = 0.5, 0.5, 0.5): as a 1 x 1 map the value is zero everywhere, and so are the derivative image and every gradient; as one
     texel of a 4 x 4 map (|v| -> 0 around its centre, where n' turns arbitrarily fast) everything stays finite."""
     res, spp, sppe = 16, 4, 4
-    tb = scene(quad_xml(normal_xml(0.3, (0.5, 0.5, 0.5)), 30.0), res, spp, sppe).tables(0)
+    tb = scene(uv_quad_xml(normal_xml(0.3, (0.5, 0.5, 0.5)), 30.0), res, spp, sppe).tables(0)
     o, img, grads = _all_modes(tb, res, spp, 0)
     assert (img == 0).all() and (_normal_texel_dimg(tb, o) == 0).all()
     for n in ("texels", "tri_info", "cam_to_world"):
         assert (grads[n] == 0).all(), n
     tex = random_normal_texels()
     tex[5] = 0.5
-    tb = scene(quad_xml(normal_xml(0.3), 0.0), res, spp, sppe, normal=tex, textured=True).tables(0)
+    tb = scene(uv_quad_xml(normal_xml(0.3), 0.0), res, spp, sppe, normal=tex, textured=True).tables(0)
     _, img, _ = _all_modes(tb, res, spp, sppe)
     assert img.max() > 0
 
@@ -181,16 +179,16 @@ def test_degenerate_normal_below_the_surface():
     """Texels with v.z < 0.  v = (0, 0, -1): n' = -n, wi'.z < 0 at every hit -- zero image, zero gradients.  v = (0.8, 0, -0.3) on the quad tilted towards +u and
     away from it: n' is below the surface, yet where it still faces the camera the lobes are evaluated about it -- the closed form, and zero where it does not."""
     res, spp, sppe = 16, 4, 4
-    tb = scene(quad_xml(normal_xml(0.3, tuple(encode((0.0, 0.0, -1.0)))), 30.0), res, spp, sppe).tables(0)
+    tb = scene(uv_quad_xml(normal_xml(0.3, tuple(encode((0.0, 0.0, -1.0)))), 30.0), res, spp, sppe).tables(0)
     o, img, grads = _all_modes(tb, res, spp, 0)
     assert (img == 0).all() and (_normal_texel_dimg(tb, o) == 0).all()
     for n in ("texels", "tri_info", "cam_to_world"):
         assert (grads[n] == 0).all(), n
     lit = []
     for tilt in (70.0, -70.0):
-        tb = scene(quad_xml(normal_xml(0.3, tuple(encode((0.8, 0.0, -0.3)))), tilt), res, spp, sppe).tables(0)
+        tb = scene(uv_quad_xml(normal_xml(0.3, tuple(encode((0.8, 0.0, -0.3)))), tilt), res, spp, sppe).tables(0)
         o, img, grads = _all_modes(tb, res, spp, sppe)
-        ref = closed_form_image(tb, host_film_samples(tb, o), spp)
+        ref = closed_form_image(tb, host_film_samples(tb, o), spp, "normal")
         lit.append(ref.max() > 0)
         assert (img[ref.sum(1) == 0] == 0).all()
         if lit[-1]:
@@ -207,11 +205,11 @@ def test_forward_equals_reverse(name):
     |lhs - rhs| <= 1e-4 x scale, as test_collocated_host.py::test_forward_equals_reverse.  The normal map's texel range receives a gradient, and the triangle-row
     gradient differs from that of the same scene without the map: the tangent-frame path carries something."""
     res, spp, sppe = 16, 4, 4
-    tb = named_scene(name, res, spp, sppe).tables(0)
+    tb = named_scene("normal", name, res, spp, sppe).tables(0)
     assert tb["material_mask"] & (1 << _abi.BSDF_MICROFACET_NORMAL)
     adj = np.random.default_rng(5).random((res * res, 3)).astype(np.float32)
     o = colloc_opts(spp, sppe, rng_offset=(2, 3, 0))
-    row, off = normal_record(tb)
+    row, off = record(tb, "normal")
     for n in NAMES:
         tan = random_tangents(tb, [n], seed=1)
         img, dimg = host_colloc_render(tb, o, mode=1, tangents=tan)
@@ -223,10 +221,10 @@ def test_forward_equals_reverse(name):
         print("normal map forward = reverse, %s %s: lhs %.6e rhs %.6e scale %.3e" % (name, n, lhs, rhs, scale))
         assert abs(lhs - rhs) <= 1e-4 * max(scale, 1e-6), (n, lhs, rhs, scale)
         if n == "texels":
-            for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("normal", normal_width(row))):
+            for key, width in (("kd", 48), ("f0", 48), ("roughness", 16), ("normal", map_words(row, "normal"))):
                 assert np.abs(grads["texels"][off[key]:off[key] + width]).max() > 0, key
         if n == "tri_info":
-            tb0 = named_scene(name, res, spp, sppe, drop_normal=True).tables(0)
+            tb0 = named_scene("normal", name, res, spp, sppe, drop_normal=True).tables(0)
             assert np.array_equal(tb0["tri_info"].detach().cpu().numpy(), tb["tri_info"].detach().cpu().numpy())
             g0 = host_colloc_rev(tb0, o, adj, want=[n])[1][n]
             assert np.abs(grads[n] - g0).max() > 1e-3 * np.abs(g0).max()
@@ -277,7 +275,7 @@ def test_ad_against_central_differences(which):
         assert tb0["material_mask"] == 4 and np.abs(host_colloc_render(tb0, o, mode=1, tangents=tan)[1]).max() <= 1e-4 * np.abs(ad).max()
     else:
         tb = _big_quad(SPP)[0].tables(0)
-        _, off = normal_record(tb)
+        _, off = record(tb, "normal")
         i = off["normal"] + 3 * 5          # texel (1, 1), an inner one; the x channel
         base = tb["texels"].detach().clone()
         v0 = float(base[i])
@@ -314,15 +312,15 @@ def test_loader_record_and_mask():
     tables() emits: type 2 / bit 2 without a map, as before; with one, type 3 / bit 3, the three slots of type 2 unchanged and the map's (offset, w, h) in
     PSDR_SLOT_K.  param_map reaches the map."""
     tex = lean_texel()
-    sc = scene(quad_xml(normal_xml(0.3, tex)), RES, SPP)
-    sc2 = scene(quad_xml(normal_xml(0.3, tex, name="normal_map")), RES, SPP)
-    plain = scene(quad_xml(microfacet_xml(0.3)), RES, SPP)
+    sc = scene(uv_quad_xml(normal_xml(0.3, tex)), RES, SPP)
+    sc2 = scene(uv_quad_xml(normal_xml(0.3, tex, name="normal_map")), RES, SPP)
+    plain = scene(uv_quad_xml(microfacet_xml(0.3)), RES, SPP)
     tb, tb2, tbp = sc.tables(0), sc2.tables(0), plain.tables(0)
     assert tbp["material_mask"] == 4 and tb["material_mask"] == 1 << _abi.BSDF_MICROFACET_NORMAL == 8
     assert plain.param_map["BSDF[id=m]"].normal_map is None
     assert np.array_equal(tb["bsdf_rec"].cpu().numpy(), tb2["bsdf_rec"].cpu().numpy()) and np.array_equal(tb["texels"].cpu().numpy(), tb2["texels"].cpu().numpy())
-    row, off = normal_record(tb)
-    rowp, offp = microfacet_record(tbp)
+    row, off = record(tb, "normal")
+    rowp, offp = record(tbp, "plain")
     assert row[0] == 3 and rowp[0] == 2 and list(row[1:13]) == list(rowp[1:13]) and list(rowp[13:16]) == [0, 1, 1]
     assert list(row[13:16]) == [off["normal"], 1, 1]
     texels = tb["texels"].cpu().numpy()
@@ -333,10 +331,10 @@ def test_loader_record_and_mask():
     bmp = normal_xml(0.3).replace('<rgb name="normalMap" value="0.5, 0.5, 1"/>',
                                   '<texture name="normalMap" type="bitmap"><string name="filename" value="./data/textures/test_texture.exr"/></texture>')
     assert "texture" in bmp
-    sb = scene(quad_xml(bmp), RES, SPP)
+    sb = scene(uv_quad_xml(bmp), RES, SPP)
     w, h = sb.param_map["BSDF[id=m]"].normal_map.resolution
     assert w > 1 and h > 1
-    rowb, _ = normal_record(sb.tables(0))
+    rowb, _ = record(sb.tables(0), "normal")
     assert list(rowb[14:16]) == [w, h]
     # requires_grad / the torch graph reaches the map: the texel pool's gradient lands in the bitmap's tensor
     ek.set_requires_gradient(b.normal_map.data)
@@ -351,18 +349,18 @@ def test_loader_record_and_mask():
 def test_refusals():
     """DirectIntegrator and PathTracer keep raising the MicrofacetBSDF message for a normal-mapped record; a mesh without texture coordinates under a normal map
     raises the new message before any native call, from every integrator's entry -- bunny_light as it is: bunny_low.obj has no texture coordinates."""
-    sc = scene(quad_xml(normal_xml(0.3, lean_texel())), RES, SPP)
+    sc = scene(uv_quad_xml(normal_xml(0.3, lean_texel())), RES, SPP)
     direct, path = psdr_cuda.DirectIntegrator(1, 1), psdr_cuda.PathTracer(3, True)
     for call in (lambda: direct.renderC(sc), lambda: direct.renderD(sc), lambda: direct.preprocess_secondary_edges(sc, 0, [2, 2, 2, 1]),
                  lambda: path.renderC(sc), lambda: path.renderD(sc), lambda: path.preprocess_path_secondary_edges(sc, 0, [2, 2, 2, 1])):
         with pytest.raises(RuntimeError, match=MESSAGE):
             call()
     psdr_cuda.CollocatedIntegrator(1.0)._check_bsdfs(sc)
-    bare = scene(plain_bunny_xml().replace("</bsdf>", '<rgb name="normalMap" value="0.5, 0.5, 1"/></bsdf>', 1), RES, SPP)
+    bare = scene(bunny_xml("plain").replace("</bsdf>", '<rgb name="normalMap" value="0.5, 0.5, 1"/></bsdf>', 1), RES, SPP)
     assert bare.tables(0)["tri_uv"] is None and bare.tables(0)["material_mask"] & 8
     colloc = psdr_cuda.CollocatedIntegrator(1.0)
     for call in (lambda: colloc.renderC(bare), lambda: colloc.renderD(bare)):
-        with pytest.raises(RuntimeError, match=NEEDS_UV):
+        with pytest.raises(RuntimeError, match=KINDS["normal"].needs_uv):
             call()
     with pytest.raises(RuntimeError, match=MESSAGE):          # the older message first, as the C ABI orders them
         direct.renderC(bare)
@@ -370,21 +368,13 @@ def test_refusals():
 
 # ---------------------------------------------------------------- 7. the same host functions under the sanitizers
 def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
-    """tests/hostcheck/colloc_normal_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with
-    -fsanitize=address,undefined for the host: render, forward and reverse on the tiny scene of the four record types; it must end clean and report what the
+    """tests/hostcheck/colloc_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with
+    -fsanitize=address,undefined for the host (hostlibs.san_program) and asked for a record of type BSDF_MICROFACET_NORMAL:
+    render, forward and reverse on the tiny scene of the four record types; it must end clean and report what the
     library reports."""
-    exe, src = os.path.join(HC_DIR, "colloc_normal_san"), os.path.join(HC_DIR, "colloc_normal_san.cpp")
-    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in HC_DEPS + [src]):
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-pthread", src, "-o", exe]
-        san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-        r = subprocess.run(cmd + san, capture_output=True, text=True)
-        if r.returncode != 0 and ("libclang_rt" in r.stderr or "sanitizer" in r.stderr.lower()):
-            # no host sanitizer runtime beside this compiler: the program still runs the same functions over the same tables, without the instrumentation
-            print("colloc_normal_san: built WITHOUT the sanitizers, the compiler's host runtime for them is missing:\n" + r.stderr[-800:])
-            r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, "colloc_normal_san does not compile:\n" + r.stderr[-3000:]
+    exe = san_program("colloc_san", HC_DEPS)
     res, spp, sppe = 8, 2, 2
-    tb = scene(mixed_xml(), res, spp, sppe, textured=True, normal="random", uv="rot37").tables(0)
+    tb = scene(mixed_xml(MIXED_IDS), res, spp, sppe, textured=True, normal="random", uv="rot37").tables(0)
     o = colloc_opts(spp, sppe, rng_offset=(1, 2, 0))
     tan = random_tangents(tb, ["tri_info", "texels", "prim_edge"], seed=3)
     adj = np.random.default_rng(4).random((res * res, 3)).astype(np.float32)
@@ -392,7 +382,7 @@ def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
     path = str(tmp_path / "tables.bin")
     write_tables_file(path, desc, keep, o, *[tan[n].detach().cpu().numpy().astype(np.float32) for n in ("tri_info", "texels", "prim_edge")], adj)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, path], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run([exe, path, str(_abi.BSDF_MICROFACET_NORMAL)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-3000:])
     got = [float(x) for x in r.stdout.split()]
     img, dimg = host_colloc_render(tb, o, mode=1, tangents=tan, nthreads=2)

@@ -10,9 +10,9 @@ import torch
 
 import oracle
 import torch_oracle as to
-from collocated_helpers import (DIFFUSE, HC_DEPS, HC_DIR, ROUGH, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, quad_xml, xml_scene)
+from collocated_helpers import (DIFFUSE, HC_DEPS, ROUGH, colloc_opts, host_colloc_render, host_colloc_rev, host_film_samples, quad_xml, xml_scene)
 from helpers import dot_tables, load_scene, random_tangents, rel_l2, tangents_wrt
-from hostlibs import cpu_desc, write_tables_file
+from hostlibs import cpu_desc, san_program, write_tables_file
 from psdr_cuda import _abi
 
 RES, SPP = 16, 4
@@ -196,18 +196,9 @@ def test_scene_without_an_emitter():
 
 # ---------------------------------------------------------------- the same host functions under the sanitizers
 def test_host_functions_run_clean_under_the_sanitizers(tmp_path):
-    """tests/hostcheck/collocated_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with -fsanitize=address,undefined for
-    the host: render, forward and reverse on one tiny scene; it must end clean and report what the library reports."""
-    exe, src = os.path.join(HC_DIR, "collocated_san"), os.path.join(HC_DIR, "collocated_san.cpp")
-    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in HC_DEPS + [src]):
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-pthread", src, "-o", exe]
-        san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-        r = subprocess.run(cmd + san, capture_output=True, text=True)
-        if r.returncode != 0 and ("libclang_rt" in r.stderr or "sanitizer" in r.stderr.lower()):
-            # no host sanitizer runtime beside this compiler: the program still runs the same functions over the same tables, without the instrumentation
-            print("collocated_san: built WITHOUT the sanitizers, the compiler's host runtime for them is missing:\n" + r.stderr[-800:])
-            r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, "collocated_san does not compile:\n" + r.stderr[-3000:]
+    """tests/hostcheck/colloc_san.cpp: a stand-alone program (its own main, no Python) over hostcheck_collocated.cpp, built with -fsanitize=address,undefined for
+    the host (hostlibs.san_program): render, forward and reverse on one tiny scene; it must end clean and report what the library reports."""
+    exe = san_program("colloc_san", HC_DEPS)
     res, spp, sppe = 8, 2, 2
     sc, _ = load_scene("cbox_rough", res=res, spp=spp, sppe=sppe)
     tb = sc.tables(0)
