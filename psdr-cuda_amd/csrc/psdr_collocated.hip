@@ -198,7 +198,7 @@ int colloc_run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL
     if (int rc = make_ctx(h, o, 0, cx)) return rc;
     const long long n = WH * nsp;
     h->slots[0] += (uint64_t) n;
-    const int own = (h->opt.own_pixels != 0 && nsp <= 64 && 64 % nsp == 0) ? 1 : 0;          // run_camera's rule
+    const int own = wave_owns_pixels(h, nsp, n);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colloc_camera<G, R, FL>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, o->spp, o->spp_begin,
                        SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
     HIP_TRY(hipGetLastError());
@@ -218,20 +218,13 @@ int colloc_render_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_t
     for (int k = 0; k < K; ++k) tv.t[k] = tangents[k];
     HIP_TRY(hipMemsetAsync(img, 0, sizeof(float) * WH * 3, s));
     HIP_TRY(hipMemsetAsync(dimg, 0, sizeof(float) * WH * 3 * K, s));
-    // geometry stays in plain fp32 when only material tables carry tangents
-    bool geo = false;
-    for (int k = 0; k < K; ++k) geo = geo || tangents[k].d_tri_info || tangents[k].d_cam_to_world;
-    if (geo) { if (int rc = colloc_run_camera<Dual<K>, Dual<K>, FL>(h, o, tv, img, dimg, s)) return rc; }
+    if (tangents_move_geometry(tangents, K)) { if (int rc = colloc_run_camera<Dual<K>, Dual<K>, FL>(h, o, tv, img, dimg, s)) return rc; }
     else { if (int rc = colloc_run_camera<float, Dual<K>, FL>(h, o, tv, img, dimg, s)) return rc; }
     if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0) {
-        LaunchCtx cx;
-        if (int rc = make_ctx(h, o, 1, cx)) return rc;
-        const long long i0 = WH * o->sppe_begin, n = WH * (o->sppe_end - o->sppe_begin);
-        h->slots[1] += (uint64_t) n;
-        const uint32_t *order = nullptr;
-        if (int rc = primary_edge_order(h, cx, i0, n, &order, s)) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colloc_edge<K, FL>), dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppe, dimg, WH * 3,
-                           h->d_counters, order);
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colloc_edge<K, FL>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, e.i0, e.n, 1.f / (float) o->sppe, dimg, WH * 3,
+                           h->d_counters, e.order);
         HIP_TRY(hipGetLastError());
     }
     return 0;          // (sppse: this integrator has no secondary-edge term)
@@ -249,11 +242,8 @@ template <int FL>
 int colloc_render_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, hipStream_t s) {
     const long long WH = (long long) h->desc.width * h->desc.height;
     if (out_img) HIP_TRY(hipMemsetAsync(out_img, 0, sizeof(float) * WH * 3, s));
-    DeviceSink<FL> sink{}; sink.g = *grads; sink.L = make_sink_layout(h, grads);
-    if ((FL & kSceneTiny) != 0 && PSDR_TINY_DIRECT_ROWS && grads->g_tri_info != nullptr && !(h->hot_identity && sink.L.hot_rows == h->desc.num_tris))
-        return fail("psdr_render_d_rev: the gradient cache of a scene without a tree does not hold every triangle row");
-    sink.L.priv_rows = 0; sink.L.priv_emitter = -1; sink.L.priv_regs = 0;          // no light samples: no private emitter rows; one vertex per slot: nothing deferred
-    sink.L.pend_rows = 0; sink.L.pend_off = 0;
+    DeviceSink<FL> sink{};
+    if (int rc = make_device_sink(h, grads, sink)) return rc;
     const int nsp = o->spp_end - o->spp_begin;
     if (o->spp > 0 && nsp > 0) {
         LaunchCtx cx;
@@ -261,19 +251,12 @@ int colloc_render_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *a
         const long long n = WH * nsp;
         h->slots[0] += (uint64_t) n;
         const bool geo = grads->g_tri_info != nullptr || grads->g_cam_to_world != nullptr;
-        const int cache_bytes = sink_bytes(sink.L);
-        plan_lds(h, cx, cache_bytes);
-        cx.off_sink = lds_bytes(cx, h);
-        const int dyn_bytes = cx.off_sink + cache_bytes;
-        if (dyn_bytes > h->lds_limit) return fail("psdr_render_d_rev: the launch needs " + std::to_string(dyn_bytes) + " bytes of LDS per workgroup (traversal stacks + gradient cache), the device offers " +
-                                                  std::to_string(h->lds_limit));
-        {
-            int32_t *r = h->rev_layout;                                 // psdr_scene_rev_layout
-            r[0] = sink.L.tex_n; r[1] = sink.L.rad_n; r[2] = sink.L.env_n; r[3] = sink.L.hot_rows; r[4] = sink.L.rep; r[8] = 0;
-            r[10] = h->hot_identity ? 1 : 0; r[14] = h->hot_rows;
-        }
+        int dyn_bytes = 0;          // no light samples: no private emitter rows; one vertex per slot: nothing deferred
+        if (int rc = plan_rev_one_vertex(h, cx, sink.L, &dyn_bytes)) return rc;
+        rev_layout_of_sink(h, sink.L, false);
+        h->rev_layout[8] = kRevFused;
 #define PSDR_LAUNCH_COLLOC_REV(GEO)                                                                                                                                      \
-        do { if (dyn_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_colloc_camera_rev<FL, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes)); \
+        do { if (int rc = allow_dynamic_lds(&k_colloc_camera_rev<FL, GEO>, dyn_bytes)) return rc;                                                                        \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_colloc_camera_rev<FL, GEO>), dim3(launch_blocks(h, n)), dim3(kBlock), dyn_bytes, s, cx, sink, o->spp, o->spp_begin, SlotDiv(nsp), n,                \
                            1.f / (float) o->spp, adj_img, out_img, h->d_counters); } while (0)
         if (geo) PSDR_LAUNCH_COLLOC_REV(true); else PSDR_LAUNCH_COLLOC_REV(false);
@@ -281,31 +264,14 @@ int colloc_render_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *a
         HIP_TRY(hipGetLastError());
     }
     if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0 && grads->g_prim_edge) {
-        LaunchCtx cx;
-        if (int rc = make_ctx(h, o, 1, cx)) return rc;
-        const long long i0 = WH * o->sppe_begin, n = WH * (o->sppe_end - o->sppe_begin);
-        h->slots[1] += (uint64_t) n;
-        // replicated gradient table (PrimaryEdgeSink), as render_rev
-        const long long pe_words = (long long) h->desc.num_prim_edges * PSDR_PEDGE_STRIDE;
-        int reps = 1;
-        while (reps < 64 && (long long) (reps * 2) * pe_words * 4 <= (64ll << 20)) reps *= 2;
-        if (n < (1ll << 18)) reps = 1;
-        if (reps > 1) {
-            const size_t need = (size_t) reps * pe_words * sizeof(float);
-            if (int rc = scratch_reserve(&h->d_pe_rep, &h->pe_rep_bytes, need, s, "primary-edge gradient replicas")) return rc;
-            HIP_TRY(hipMemsetAsync(h->d_pe_rep, 0, need, s));
-        }
-        const PrimaryEdgeSink<FL> pe_sink{reps > 1 ? reinterpret_cast<float *>(h->d_pe_rep) : grads->g_prim_edge, pe_words, reps};
-        const uint32_t *order = nullptr;
-        if (int rc = primary_edge_order(h, cx, i0, n, &order, s)) return rc;
-        h->rev_layout[9] = reps; h->rev_layout[15] = order != nullptr ? 1 : 0;
-        hipLaunchKernelGGL(k_colloc_edge_rev<FL>, dim3(launch_blocks(h, n, big_launch_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, pe_sink, i0, n, 1.f / (float) o->sppe, adj_img,
-                           h->d_counters, order);
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
+        PrimaryEdgeSink<FL> pe_sink;
+        if (int rc = begin_pe_replicas(h, grads, e, pe_sink, s)) return rc;
+        hipLaunchKernelGGL(k_colloc_edge_rev<FL>, dim3(launch_blocks(h, e.n, big_launch_per_cu(h, e.n))), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, pe_sink, e.i0, e.n, 1.f / (float) o->sppe,
+                           adj_img, h->d_counters, e.order);
         HIP_TRY(hipGetLastError());
-        if (reps > 1) {
-            hipLaunchKernelGGL(k_sum_replicas, dim3((unsigned) ((pe_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, grads->g_prim_edge, reinterpret_cast<const float *>(h->d_pe_rep), pe_words, reps);
-            HIP_TRY(hipGetLastError());
-        }
+        if (int rc = end_pe_replicas(h, grads, pe_sink, s)) return rc;
     }
     return 0;
 }

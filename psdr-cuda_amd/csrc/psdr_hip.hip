@@ -467,42 +467,6 @@ int scratch_reserve(void **buf, size_t *have, size_t need, hipStream_t s, const 
     return 0;
 }
 
-// Grid of the grid-stride kernels: at most per_cu workgroups per CU (16 by default; the forward camera kernels
-// choose theirs, psdr_kernels.h camera_blocks_per_cu; the reverse kernels zero and flush a gradient cache per
-// workgroup and are flat between 8 and 24).
-int launch_blocks(const psdr_scene_s *h, long long n, int per_cu) {
-    const int forced = h->opt.blocks_per_cu;
-    const long long need = (n + kBlock - 1) / kBlock;
-    const long long cap = (long long) h->num_cus * (forced ? forced : per_cu);
-    return (int) std::max(1LL, std::min(need, cap));
-}
-
-// LDS plan of one launch: stacks sized by the tree depth, the rest of a 40 KB budget (4 workgroups
-// per CU) filled with the top of the BVH, then the leaf triangles, then the TriangleInfo rows.
-constexpr int kLdsBudget = 40 * 1024;
-static bool tiny_only(const psdr_scene_s *h) { return h->n_tiny > 0 && h->n_blas == 0; }
-// entries of face_cmf / face_pmf the emitters reference (host copy of emitter_i, psdr_bvh_build)
-static int emitter_faces(const psdr_scene_s *h) {
-    int n = 0;
-    for (int e = 0; e < h->desc.num_emitters && (size_t) (e + 1) * PSDR_EMITTER_I_STRIDE <= h->emitter_i.size(); ++e)
-        n = std::max(n, h->emitter_i[(size_t) e * PSDR_EMITTER_I_STRIDE + 3] + h->emitter_i[(size_t) e * PSDR_EMITTER_I_STRIDE + 2]);
-    return n;
-}
-// A scene without a tree whose small tables fit the LDS block of the kSceneTiny kernel instances (a few KB): every launch on it stages
-// them (plan_lds) and variant_of picks those instances.  PSDR_TINY_VARIANTS=0: the general instances (A/B, tools).
-constexpr int kLdsTexels = 256, kLdsTexelTangents = 3;
-// the mesh-level tables (mesh -> bsdf / emitter, BSDF and emitter records, the emitters' face distributions) fit the LDS block of the kernels
-static bool small_tables_fit(const psdr_scene_s *h) {
-    const psdr_scene_desc &d = h->desc;
-    return d.env_emitter < 0 && d.num_meshes <= 64 && d.num_bsdfs <= 32 && d.num_emitters >= 0 && d.num_emitters <= 8 &&
-           (d.num_emitters == 0 || (d.face_cmf && d.face_pmf)) && emitter_faces(h) <= 64;
-}
-static bool tiny_tables_ok(const psdr_scene_s *h) {
-    return h->opt.tiny_variants != 0 && tiny_only(h) && small_tables_fit(h);
-}
-// The kernels of a two-level scene read the mesh-level tables from LDS and have no other path (psdr_device.h Tab<FL>::lds_small): such a tree
-// is only built, and only kept, while they fit (psdr_bvh_build, ensure_tree_kind).
-static bool forest_tables(const psdr_scene_s *h) { return PSDR_FOREST_LDS_TABLES && h->n_blas > 0; }
 // Which tree the launches on this scene walk: the 4-wide quantised tree exactly where the scene's kernel variant is compiled for it (flag set 6:
 // rough conductor + two-level tree, psdr_variant.hip) -- measured 5-10 % ahead on the 50 k-triangle interior, level or behind elsewhere
 // (profiles/r03_bvh4_ab.txt).  k_trace (this unit) carries both walks and follows the scene.
@@ -510,52 +474,6 @@ static bool use_wide_tree(const psdr_scene_s *h, bool forest) {
     if (h->opt.wide == 0) return false;                 // never (the variant-6 kernels then cannot run: tools only)
     return forest && h->has_rough && h->desc.env_emitter < 0;
 }
-
-// traversal-stack entries per lane: none when no launch on this scene ever walks a tree
-static int stack_entries_of(const psdr_scene_s *h) { return tiny_only(h) ? 0 : (h->wide ? h->stack_need4 + 1 : std::min(kBvhStack, h->bvh_depth + 2)); }
-static int staged_nodes_of(const psdr_scene_s *h) { return h->wide ? h->num_nodes4 : h->num_nodes; }
-int plan_lds(const psdr_scene_s *h, LaunchCtx &cx, int reserved) {
-    // the plain diffuse variant runs renderC at 5 workgroups per CU: 28 KB each (C4 PathTracer(3) 40.0 -> 37.6 ms,
-    // C3 3.26 -> 3.15 ms; 32 KB is already one workgroup less)
-    const int forced = h->opt.lds_budget;
-    const bool lean = !h->has_rough && h->desc.env_emitter < 0;
-    const int budget = forced ? forced : (lean ? 28 * 1024 : kLdsBudget);
-    const int stack_bytes = stack_entries_of(h) * kBlock * 4;
-    int room = std::max(0, budget - reserved - stack_bytes);
-    // a scene without a tree (all primitives in the kernel arguments) ALWAYS stages its <= 16 TriangleInfo rows (1.5 KB): the kSceneTiny
-    // kernel instances have no global-memory fallback for them (psdr_device.h load_tri_f)
-    if (tiny_only(h)) room = std::max(room, staged_nodes_of(h) * kLdsNodeStride + h->num_btris * 48 + h->desc.num_tris * 96);
-    SceneView &sc = cx.sc;
-    int off = 0;
-    sc.n_lnodes = std::min(staged_nodes_of(h), room / kLdsNodeStride); sc.off_lnodes = off; off += sc.n_lnodes * kLdsNodeStride; room -= sc.n_lnodes * kLdsNodeStride;
-    sc.n_lbtris = (sc.n_lnodes == staged_nodes_of(h)) ? std::min(h->num_btris, room / 48) : 0;
-    sc.off_lbtris = off; off += sc.n_lbtris * 48; room -= sc.n_lbtris * 48;
-    sc.n_ltri = (sc.n_lbtris == h->num_btris) ? std::min(h->desc.num_tris, room / 96) : 0;
-    sc.off_ltri = off; off += sc.n_ltri * 96;
-    sc.off_lprim = off; off += h->n_tiny * kTinyHitWords * 4;          // hit rows of the kernel-argument primitives (resolve_tiny_hit)
-    // the small tables of a scene without a tree (psdr_device.h Tab<FL>, staged by setup_lds): 16-byte aligned blocks
-    sc.lt_trimesh = sc.lt_meshbsdf = sc.lt_meshemitter = sc.lt_bsdf = sc.lt_emf = sc.lt_emi = sc.lt_fcmf = sc.lt_fpmf = sc.lt_uv = sc.lt_tex = sc.lt_ecmf = sc.lt_epmf = -1;
-    sc.lt_nfaces = 0; sc.lt_occ = -1; sc.occ = nullptr;
-    const bool all_tables = tiny_tables_ok(h);
-    if (all_tables || forest_tables(h)) {
-        auto take = [&](int words) { const int o = off; off += (words * 4 + 15) / 16 * 16; return o; };
-        const psdr_scene_desc &d = h->desc;
-        sc.lt_nfaces = emitter_faces(h);
-        if (all_tables) sc.lt_trimesh = take(d.num_tris);          // per-triangle tables: only where every triangle is a kernel-argument primitive
-        sc.lt_meshbsdf = take(d.num_meshes); sc.lt_meshemitter = take(d.num_meshes);
-        sc.lt_bsdf = take(std::max(d.num_bsdfs, 1) * PSDR_BSDF_STRIDE);
-        sc.lt_emf = take(d.num_emitters * PSDR_EMITTER_F_STRIDE); sc.lt_emi = take(d.num_emitters * PSDR_EMITTER_I_STRIDE);
-        sc.lt_fcmf = take(sc.lt_nfaces); sc.lt_fpmf = take(sc.lt_nfaces);
-        if (d.num_emitters > 1 && d.emitter_cmf && d.emitter_pmf) { sc.lt_ecmf = take(d.num_emitters); sc.lt_epmf = take(d.num_emitters); }
-        if (all_tables && d.tri_uv) sc.lt_uv = take(d.num_tris * PSDR_TRIUV_STRIDE);
-        if (d.num_texels > 0 && d.num_texels <= kLdsTexels) sc.lt_tex = take(d.num_texels * (1 + kLdsTexelTangents));      // value pool + up to 3 tangent pools (forward mode)
-        if (all_tables && h->have_occ && h->d_occ != nullptr) { sc.occ = h->d_occ; sc.lt_occ = take(d.num_tris * d.num_tris); }   // occluder rows of the light rays (<= 32 x 32 words)
-    }
-    sc.lt_end = off;
-    cx.off_stack = off;
-    return off + stack_bytes;
-}
-int lds_bytes(const LaunchCtx &cx, const psdr_scene_s *h) { return cx.off_stack + stack_entries_of(h) * kBlock * 4; }
 
 // the part of the tree that travels in the kernel arguments (tiny scenes, two-level trees)
 void fill_top(const psdr_scene_s *h, SceneView &sc) {
@@ -610,64 +528,6 @@ int check_microfacet(const psdr_scene_s *h, const psdr_render_opts *o) {
     // ... and PSDR_BSDF_MICROFACET_HEIGHT its surface-gradient basis
     if ((h->desc.material_mask & (1u << PSDR_BSDF_MICROFACET_HEIGHT)) != 0 && h->desc.tri_uv == nullptr) return fail("a height map needs texture coordinates");
     return 0;
-}
-
-// Strategy choice: a PURE FUNCTION of the scene and the options (round 3; it used to follow the survival ratio the previous PathTracer
-// call on the handle had measured, so the same call could run either strategy depending on the call history -- and the two agree only
-// to the rounding of separately compiled fp32 kernels, up to 1e-3 on a low-spp GGX scene where one firefly sample flips).
-// Measured on MI355X (tools/perf_cases.py): in a closed room almost every path survives every bounce, compaction buys nothing and the
-// fused kernel is 1.1-1.9x ahead; in an open scene (bunny_light: 2.5 of 7 possible rays per path) the wavefront is 1.35-1.5x ahead.
-// "Room" = what psdr_bvh_build recognised as one: all primitives in the kernel arguments (the Cornell box) or a two-level tree (>= 6 inline
-// wall triangles around the meshes); everything else (objects under a light, height fields, environment-lit scenes) counts as open.
-bool open_scene(const psdr_scene_s *h) { return !(h->n_blas > 0 || (h->n_tiny > 0 && h->n_blas == 0)); }
-bool use_wavefront(const psdr_scene_s *h, const psdr_render_opts *o) {
-    if (o->integrator != PSDR_INTEGRATOR_PATH || o->max_depth > 250) return false;
-    if (h->desc.num_tris >= (1 << 29)) return false;                // a stream record keeps its triangle in 29 bits (psdr_kernels.h kWfTriMask)
-    if (o->flags & PSDR_FLAG_FUSED) return false;
-    if (o->flags & PSDR_FLAG_WAVEFRONT) return true;
-    if (o->max_depth < 2) return false;
-    if (open_scene(h)) return true;                                 // most paths die early, compaction pays
-    const long long n = (long long) h->desc.width * h->desc.height * (o->spp_end - o->spp_begin);
-    // two-level scene (a room with objects): the TRACED wavefront -- in the fused kernel a wave pays the slowest lane's tree walk at every
-    // closest_hit although only a fifth of the rays enter a tree; with the walks in the dense trace kernel between the stages C4's shard takes
-    // 18.2 ms against 25.8 fused (21.8 class-binned), the 50 k-triangle interior 2.8 against 4.6, cbox_bunny at 4 M slots 1.6 against 2.1
-    // (profiles/r04_traced_first.txt); below 2^16 slots the seven launches cost more than the walks
-    if (traced_wavefront(h)) return n >= (1ll << 16);
-    // without the trace kernel (PSDR_WF_TRACED=0): the class-binned streams (psdr_kernels.h) are ahead of the fused kernel on large launches only --
-    // C4 shard (67 M slots) 27.5 against 29.6 ms; at 4 M slots their extra launches and stream traffic cost more than they save (3.7 against 2.9 ms)
-    return h->n_blas > 0 && h->wf_binned && n >= (1ll << 25);
-}
-
-SinkLayout make_sink_layout(const psdr_scene_s *h, const psdr_grads *g) {
-    SinkLayout L{};
-    int off = 0;
-    L.cam_off = off; off += 16;
-    if (g->g_env_f && h->desc.env_emitter >= 0) { L.env_off = off; L.env_n = PSDR_ENV_WORDS; off += PSDR_ENV_WORDS; }
-    const int nt = h->desc.num_texels, nr = h->desc.num_emitters * 3;
-    if (g->g_texels && nt > 0 && nt <= 2048) { L.tex_off = off; L.tex_n = nt; off += nt; }
-    if (g->g_emitter_rad && nr > 0 && nr <= 256) { L.rad_off = off; L.rad_n = nr; off += nr; }
-    if (g->g_tri_info && h->hot_rows > 0) {
-        const int rows = std::min(h->hot_rows, (kSinkCacheWords - off) / PSDR_TRI_STRIDE);
-        // slots >= rows (cache too small for all of them) fall back to global atomics in add_tri
-        if (rows > 0) { L.hot_off = off; L.hot_rows = rows; L.hot_map = h->d_hot_map; L.hot_tris = h->d_hot_tris; off += rows * PSDR_TRI_STRIDE; }
-    }
-    L.total = off;
-    L.stride = off | 1;
-    L.rep = 1;
-    // 2 copies bought 6 % on C2, more nothing: 4 at most, so that a small scene's cache stays a few KB of LDS
-    const int max_rep = h->opt.sink_rep;
-    while (L.rep * 2 <= max_rep && L.rep * 2 * L.stride <= kSinkCacheWords) L.rep *= 2;
-    // lane-private rows: the leading hot slots are emitter 0's triangles (build_bvh)
-    const bool priv_on = h->opt.sink_private != 0;
-    L.priv_tri[0] = L.priv_tri[1] = -1; L.priv_slot[0] = L.priv_slot[1] = 0; L.priv_emitter = -1;
-    if (priv_on && L.hot_rows > 0 && h->desc.num_emitters > 0 && h->desc.env_emitter != 0) {
-        const int32_t *ei = h->emitter_i.data();
-        const int n = std::min(std::min(ei[2], 2), L.hot_rows);
-        for (int r = 0; r < n; ++r) { L.priv_tri[r] = ei[1] + r; L.priv_slot[r] = h->hot_identity ? ei[1] + r : r; }
-        L.priv_rows = n;
-        if (n > 0) { L.priv_off = (L.rep * L.stride + 3) / 4 * 4; if (L.rad_n) L.priv_emitter = 0; }
-    }
-    return L;
 }
 
 // The tree kind follows the kernel variant, the variant follows material_mask -- which psdr_scene_set_tables can change without a rebuild (a
@@ -899,7 +759,6 @@ int bvh4_build(psdr_scene_s *h, const std::vector<BvhNode> &nodes, const std::ve
 }
 
 // ---- the dense trace kernel of the traced wavefront
-bool traced_wavefront(const psdr_scene_s *h) { return h->traced_enabled && h->n_blas > 0 && h->num_nodes4 > 0 && h->d_nodes4 != nullptr; }
 int launch_wf_trace(psdr_scene_s *h, const float4 *req, const int32_t *count, long long sub_cap, float4 *hit, hipStream_t s, bool ign) {
     TraceArgs a{};
     a.sec_edge_faces = h->desc.sec_edge_faces;
@@ -934,7 +793,7 @@ int launch_wf_trace(psdr_scene_s *h, const float4 *req, const int32_t *count, lo
     const int dyn = a.off_stack + stack_bytes;
 #define PSDR_LAUNCH_TRACE_I(MULTI, OVF, IGN, WPE)                                                                                                           \
     do { static bool attr_set = false;                                                                                                                      \
-         if (!attr_set) { HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wf_trace<MULTI, OVF, IGN, WPE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024)); attr_set = true; } \
+         if (!attr_set) { if (int rc = allow_dynamic_lds(&k_wf_trace<MULTI, OVF, IGN, WPE>, 160 * 1024 - 1024)) return rc; attr_set = true; }                     \
          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wf_trace<MULTI, OVF, IGN, WPE>), dim3(grid), dim3(kTraceBlock), dyn, s, a); } while (0)
 #define PSDR_LAUNCH_TRACE(MULTI, OVF) do { if (ign) { if (wg2) PSDR_LAUNCH_TRACE_I(MULTI, OVF, true, 8); else PSDR_LAUNCH_TRACE_I(MULTI, OVF, true, 4); } else if (wg2) PSDR_LAUNCH_TRACE_I(MULTI, OVF, false, 8); else PSDR_LAUNCH_TRACE_I(MULTI, OVF, false, 4); } while (0)
     if (h->n_blas > 1) { if (ovf) PSDR_LAUNCH_TRACE(true, true); else PSDR_LAUNCH_TRACE(true, false); }
@@ -963,51 +822,17 @@ int probe_buffers(psdr_scene_s *h, long long slots, int rays_per_slot, ProbeBuff
     return 0;
 }
 
-// kernel variant of the scene: bit 0 = environment map present, bit 1 = a rough conductor may be present
-const VariantOps *variant_of(const psdr_scene_s *h) {
-    int fl = (h->desc.env_emitter >= 0 ? kSceneEnv : 0) | (h->has_rough ? kSceneRough : 0) | (h->n_blas > 0 ? kSceneForest : 0);
-    if (tiny_tables_ok(h)) fl |= kSceneTiny;
-    switch (fl) {
-        case 0: return variant_ops_0();
-        case 1: return variant_ops_1();
-        case 2: return variant_ops_2();
-        case 3: return variant_ops_3();
-        case 4: return variant_ops_4();
-        case 8: return variant_ops_8();
-        case 10: return variant_ops_10();
-        default: return variant_ops_6();      // 6; psdr_bvh_build never builds a two-level tree under an environment map
+// kernel variant of the scene (scene_flag_set), and the same choice for the kernels of psdr_path_sedge.hip and of psdr_collocated.hip
+#define PSDR_OPS_OF(OPS)                                                                                                              \
+    switch (scene_flag_set(h)) {                                                                                                      \
+        case 0: return OPS##0(); case 1: return OPS##1(); case 2: return OPS##2(); case 3: return OPS##3();                          \
+        case 4: return OPS##4(); case 8: return OPS##8(); case 10: return OPS##10();                                                 \
+        default: return OPS##6();      /* 6; psdr_bvh_build never builds a two-level tree under an environment map */                 \
     }
-}
-// the same choice for the kernels of psdr_path_sedge.hip
-const PathSedgeOps *path_sedge_of(const psdr_scene_s *h) {
-    int fl = (h->desc.env_emitter >= 0 ? kSceneEnv : 0) | (h->has_rough ? kSceneRough : 0) | (h->n_blas > 0 ? kSceneForest : 0);
-    if (tiny_tables_ok(h)) fl |= kSceneTiny;
-    switch (fl) {
-        case 0: return path_sedge_ops_0();
-        case 1: return path_sedge_ops_1();
-        case 2: return path_sedge_ops_2();
-        case 3: return path_sedge_ops_3();
-        case 4: return path_sedge_ops_4();
-        case 8: return path_sedge_ops_8();
-        case 10: return path_sedge_ops_10();
-        default: return path_sedge_ops_6();
-    }
-}
-// ... and for the kernels of psdr_collocated.hip
-const CollocatedOps *collocated_of(const psdr_scene_s *h) {
-    int fl = (h->desc.env_emitter >= 0 ? kSceneEnv : 0) | (h->has_rough ? kSceneRough : 0) | (h->n_blas > 0 ? kSceneForest : 0);
-    if (tiny_tables_ok(h)) fl |= kSceneTiny;
-    switch (fl) {
-        case 0: return collocated_ops_0();
-        case 1: return collocated_ops_1();
-        case 2: return collocated_ops_2();
-        case 3: return collocated_ops_3();
-        case 4: return collocated_ops_4();
-        case 8: return collocated_ops_8();
-        case 10: return collocated_ops_10();
-        default: return collocated_ops_6();
-    }
-}
+const VariantOps *variant_of(const psdr_scene_s *h) { PSDR_OPS_OF(variant_ops_) }
+const PathSedgeOps *path_sedge_of(const psdr_scene_s *h) { PSDR_OPS_OF(path_sedge_ops_) }
+const CollocatedOps *collocated_of(const psdr_scene_s *h) { PSDR_OPS_OF(collocated_ops_) }
+#undef PSDR_OPS_OF
 }  // namespace psdr_host
 using namespace psdr_host;
 

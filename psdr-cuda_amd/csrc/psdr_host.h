@@ -1,5 +1,5 @@
 // psdr_host.h -- what the translation units of libpsdr_hip.so share: the launch context, the scene
-// handle, the host-side launch helpers (defined in psdr_hip.hip) and the table of kernel variants.
+// handle, the host-side launch helpers (planning: psdr_plan.h, included at the end; the rest defined in psdr_hip.hip) and the table of kernel variants.
 //
 // The kernels are compiled once per SCENE FLAG SET (TangentView FLAGS in psdr_device.h: environment map
 // present, rough conductor present) in separate translation units (psdr_variant.hip with
@@ -312,28 +312,28 @@ constexpr int kRayCounters = 64, kRayCounterStride = 16;     // d_counters: 64 c
 // wavefront streams and trace-request queues: 64 sub-streams / sub-queues, their counters on their own 128-byte lines (psdr_kernels.h)
 constexpr int kWfSub = 64, kWfCountStride = 32;
 
+#define HIP_TRY(expr)                                                                              \
+    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return psdr_host::fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 namespace psdr_host {
 int fail(const std::string &m);
+// a launch with more than 48 KB of dynamic LDS needs the kernel's attribute raised first
+template <class Kernel> int allow_dynamic_lds(Kernel *kernel, int bytes) {
+    if (bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return 0;
+}
 // Growth of a per-handle scratch buffer INSIDE a render call: stream-ordered (hipFreeAsync / hipMallocAsync on the call's stream --
 // no device-wide synchronise on the hot path of the first large call or after a size change), and refused with a clear message when the device does
 // not have the memory (the traced wavefront takes 16 GB for a 2^26-slot chunk: fine for eight ranks on eight GPUs, not for two processes on one).
 int scratch_reserve(void **buf, size_t *have, size_t need, hipStream_t s, const char *what);
 long long fit_chunk(long long chunk, size_t bytes_per_slot, size_t fixed_bytes, size_t have);      // the largest power-of-two fraction of `chunk` whose workspace the device can hold now
 inline int workspace_reserve(psdr_scene_s *h, size_t need, hipStream_t s) { return scratch_reserve(&h->d_ws, &h->ws_bytes, need, s, "wavefront workspace (path-state streams + trace requests)"); }
-int launch_blocks(const psdr_scene_s *h, long long n, int per_cu = 16);
-int plan_lds(const psdr_scene_s *h, LaunchCtx &cx, int reserved = 0);
-int lds_bytes(const LaunchCtx &cx, const psdr_scene_s *h);
 void fill_top(const psdr_scene_s *h, SceneView &sc);
 constexpr int kMaxInlineTris = 2 * kTinyTris;      // inline triangles of a two-level tree before pairing
 int make_ctx(psdr_scene_s *h, const psdr_render_opts *o, int sampler, LaunchCtx &cx);
-bool use_wavefront(const psdr_scene_s *h, const psdr_render_opts *o);
-// traced wavefront (psdr_hip.hip k_wf_trace): the scene has a two-level tree whose 4-wide forest is on the device
-bool traced_wavefront(const psdr_scene_s *h);
 int launch_wf_trace(psdr_scene_s *h, const float4 *req, const int32_t *count, long long sub_cap, float4 *hit, hipStream_t s, bool ign = false);
 // Probe / final launches of the fused kernels on two-level scenes (psdr_kernels.h): the buffers between the probe pass, the trace kernel and the final pass
 struct ProbeBuffers { float4 *hit; uint32_t *mask; float4 *req; int32_t *count; long long sub_cap; };
 int probe_buffers(psdr_scene_s *h, long long slots, int rays_per_slot, ProbeBuffers &pb, hipStream_t s, int per_cu = 16);   // per_cu: workgroups per CU of the probe launch (sizes the request queues)
-SinkLayout make_sink_layout(const psdr_scene_s *h, const psdr_grads *g);
 inline int sink_bytes_base(const SinkLayout &L) { return (L.priv_rows > 0 && !L.priv_regs) ? (L.priv_off + kPrivWords * kBlock) * 4 : (L.rep * L.stride * 4 + 15) / 16 * 16; }
 inline int sink_bytes(const SinkLayout &L) { return L.pend_rows > 0 ? (L.pend_off + L.pend_rows * kPendWords * kBlock) * 4 : sink_bytes_base(L); }
 // reserve the deferred-row block behind the cache and the private block: call when the layout is otherwise final
@@ -395,5 +395,4 @@ const VariantOps *variant_ops_8();      // no tree at all (kSceneTiny: every pri
 const VariantOps *variant_ops_10();     // no tree, rough conductor
 }  // namespace psdr_host
 
-#define HIP_TRY(expr)                                                                              \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return psdr_host::fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+#include "psdr_plan.h"

@@ -1733,29 +1733,66 @@ __global__ __launch_bounds__(kBlock) void k_secondary_edge_rev(LaunchCtx cx, Dev
 
 
 // ============================================================================ launch drivers
-// Grid of the forward camera kernels: finer workgroups balance image regions of different cost better (C2 +4.5 %,
-// C4 PathTracer(3) shard 37.4 -> 34.2 ms at 40 per CU instead of 16), but every workgroup stages its share of the
-// scene in LDS first: on a 4 M-slot launch of an open scene (bunny_light) 40 per CU is 9-15 % SLOWER.  So: 40 when
-// nothing is staged (tiny scene) or when a workgroup still makes >= 8 trips of its grid-stride loop, else 16.
-inline int camera_blocks_per_cu(const psdr_scene_s *h, long long n) {
-    if (h->opt.camera_blocks > 0) return h->opt.camera_blocks;          // experiments (psdr_scene_set_option)
-    if (h->has_rough) return 16;
-    if (h->n_tiny > 0 && h->n_blas == 0) return 40;
-    // tree scenes (lean variants): pixels on a mesh cost several times a wall pixel and neighbouring pixels share a workgroup, so the hardware's
-    // workgroup scheduler balances the launch better the finer the grid -- two slots per thread, 16..64 workgroups per CU (cbox_bunny 256^2 spp 64:
-    // PathTracer(3) 2.51 -> 2.37 ms, (6) 4.17 -> 3.90 against 16; the C4 shard's fused launch 25.8 -> 24.8 against 40)
-    const long long fit = n / ((long long) kBlock * h->num_cus * 2);
-    return (int) std::max(16LL, std::min(64LL, fit));
+// ---- launch steps the drivers of every translation unit share (the rules behind them: psdr_plan.h)
+// The gradient sink of a reverse call.  The instances of scenes without a tree address a triangle's cached row directly (DeviceSink::add_tri): every row cached, slot == triangle
+template <int FL> int make_device_sink(const psdr_scene_s *h, const psdr_grads *grads, DeviceSink<FL> &sink) {
+    sink.g = *grads; sink.L = make_sink_layout(h, grads);
+    if ((FL & kSceneTiny) != 0 && PSDR_TINY_DIRECT_ROWS && grads->g_tri_info != nullptr && !(h->hot_identity && sink.L.hot_rows == h->desc.num_tris))
+        return fail("psdr_render_d_rev: the gradient cache of a scene without a tree does not hold every triangle row");
+    return 0;
 }
-// slots per chunk of the launches that keep per-slot state between kernels (wavefront streams, reverse-mode records, probe buffers): 2^log2_default,
-// or what psdr_scene_set_option("chunk_log2", ...) says (tests: chunk boundaries on small scenes)
-// workgroups per CU of the large launches that measured faster on a finer grid (traced wavefront stages, primary-edge reverse kernel, secondary-edge filter of a
-// two-level scene): 16, up to 40 where a workgroup still makes >= 8 trips of its grid-stride loop (profiles/r04_wf_grid_abk.txt)
-inline int big_launch_per_cu(const psdr_scene_s *h, long long n) { return (int) std::max(16LL, std::min(40LL, n / ((long long) kBlock * h->num_cus * 8))); }
-inline long long launch_chunk(const psdr_scene_s *h, int log2_default) { return 1ll << (h->opt.chunk_log2 > 0 ? h->opt.chunk_log2 : log2_default); }
-// DirectIntegrator(1, 1) camera launches on a two-level scene run as probe pass + dense trace kernel + final pass (from 2^16 slots)
-inline bool probe_direct(const psdr_scene_s *h, const psdr_render_opts *o, long long n) {
-    return traced_wavefront(h) && h->opt.probe != 0 && o->bsdf_samples == 1 && o->light_samples == 1 && !(o->flags & PSDR_FLAG_FUSED) && n >= (1ll << 16);
+// geometry stays in plain fp32 when only material / emitter tables carry tangents
+inline bool tangents_move_geometry(const psdr_tangents *tangents, int K) {
+    bool geo = false;
+    for (int k = 0; k < K; ++k) geo = geo || tangents[k].d_tri_info || tangents[k].d_cam_to_world;
+    return geo;
+}
+// Prologue of an edge term, sampler 1 (primary edges: sppe) or 2 (secondary edges: sppse): the launch context, the term's slots [i0, i0 + n) of the call's
+// shard, the handle's slot counter; primary edges: their slots sorted by pixel (nullptr: unsorted)
+struct EdgeLaunch { LaunchCtx cx; long long i0, n; const uint32_t *order; };
+inline int begin_edge_term(psdr_scene_s *h, const psdr_render_opts *o, int sampler, EdgeLaunch &e, hipStream_t s) {
+    if (int rc = make_ctx(h, o, sampler, e.cx)) return rc;
+    const long long WH = (long long) h->desc.width * h->desc.height;
+    const int begin = sampler == 1 ? o->sppe_begin : o->sppse_begin, end = sampler == 1 ? o->sppe_end : o->sppse_end;
+    e.i0 = WH * begin; e.n = WH * (end - begin);
+    h->slots[sampler] += (uint64_t) e.n;
+    e.order = nullptr;
+    return sampler == 1 ? primary_edge_order(h, e.cx, e.i0, e.n, &e.order, s) : 0;
+}
+// Replicated gradient table of a primary-edge reverse launch (see PrimaryEdgeSink): the copies (primary_edge_replicas) live in a scratch buffer, zeroed
+// here; end_pe_replicas, behind the launch, folds them into the caller's table
+template <int FL> int begin_pe_replicas(psdr_scene_s *h, const psdr_grads *grads, const EdgeLaunch &e, PrimaryEdgeSink<FL> &pe_sink, hipStream_t s) {
+    const long long pe_words = (long long) h->desc.num_prim_edges * PSDR_PEDGE_STRIDE;
+    const int reps = primary_edge_replicas(pe_words, e.n);
+    if (reps > 1) {
+        const size_t need = (size_t) reps * pe_words * sizeof(float);
+        if (int rc = scratch_reserve(&h->d_pe_rep, &h->pe_rep_bytes, need, s, "primary-edge gradient replicas")) return rc;
+        HIP_TRY(hipMemsetAsync(h->d_pe_rep, 0, need, s));
+    }
+    pe_sink = PrimaryEdgeSink<FL>{reps > 1 ? reinterpret_cast<float *>(h->d_pe_rep) : grads->g_prim_edge, pe_words, reps};
+    h->rev_layout[9] = reps; h->rev_layout[15] = e.order != nullptr ? 1 : 0;
+    return 0;
+}
+template <int FL> int end_pe_replicas(psdr_scene_s *h, const psdr_grads *grads, const PrimaryEdgeSink<FL> &pe_sink, hipStream_t s) {
+    if (pe_sink.reps > 1) {
+        hipLaunchKernelGGL(k_sum_replicas, dim3((unsigned) ((pe_sink.rep_stride + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, grads->g_prim_edge,
+                           reinterpret_cast<const float *>(h->d_pe_rep), pe_sink.rep_stride, pe_sink.reps);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+// First two passes of a DirectIntegrator(1, 1) camera launch on a two-level scene (probe_direct), for the slots [c0, c0 + nc) of one chunk: the probe pass
+// (primary hit + requests for the vertex' two rays that enter a tree box; cx stages the scene like a forward kernel) and the dense trace kernel.  The
+// final pass reads pb.hit / pb.mask.
+template <int FL> int probe_and_trace(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCtx &cx, long long c0, long long nc, ProbeBuffers &pb, hipStream_t s) {
+    const int probe_per_cu = big_launch_per_cu(h, nc);          // k_direct_probe 951 -> 879 us at 40 per CU on the C4 shard (profiles/r04_wf_grid_abk.txt)
+    if (int rc = probe_buffers(h, nc, 3, pb, s, probe_per_cu)) return rc;
+    const TraceQueue tq{pb.req, pb.count, pb.sub_cap};
+    const int blocks = (launch_blocks(h, nc, probe_per_cu) + kWfSub - 1) / kWfSub * kWfSub;
+    hipLaunchKernelGGL(k_direct_probe<FL>, dim3(blocks), dim3(kBlock), lds_bytes(cx, h), s, cx, TangentView<0, FL>{}, o->spp, o->spp_begin, SlotDiv(o->spp_end - o->spp_begin), c0, nc, tq,
+                       pb.hit, pb.mask, make_rng_jump(o->rng_offset[0] + 2));
+    HIP_TRY(hipGetLastError());
+    return launch_wf_trace(h, pb.req, pb.count, pb.sub_cap, pb.hit, s);
 }
 // The handle's seed table for a fused camera launch of n = WH * nsp slots on stream s (k_seed_fill above), or nullptr: the launch runs the kernels that seed their
 // streams themselves -- option seed_cache 0, a launch above 2^seed_cache_log2 slots (16 bytes per slot: 512 MB at the default 25; the 1024^2 x 512 spp launches of
@@ -1798,32 +1835,22 @@ int run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, 
     if (int rc = make_ctx(h, o, 0, cx)) return rc;
     const long long n = WH * nsp;
     h->slots[0] += (uint64_t) n;
-    // every pixel's samples of the launch in one wave: the camera kernels store their pixels instead of adding to them (k_camera `own`; chunks start at multiples of 2^24)
-    const int own = (h->opt.own_pixels != 0 && nsp <= 64 && 64 % nsp == 0) ? 1 : 0;
     // DirectIntegrator(1, 1) on a two-level scene: probe pass (primary hit + requests for the vertex' two rays that enter a tree box) -> dense trace
     // kernel -> this kernel compiled with kScenePre (no tree walk: primitives + hit rows), chunk by chunk.  C3 forward geometry duals 1.31 -> 0.73 ms
     // (0.21 + 0.19 + 0.33), C4 shard reverse 16.0 -> 14.0 ms
     if constexpr ((FL & kSceneForest) != 0) {
         if (o->integrator == PSDR_INTEGRATOR_DIRECT && probe_direct(h, o, n)) {
-            const TangentView<0, FL> tv0{};
             TV<R, FL | kScenePre> tvp;
             for (int k = 0; k < (ad_traits<R>::K > 0 ? ad_traits<R>::K : 1); ++k) tvp.t[k] = tv.t[k];
             tvp.live = tv.live;
             LaunchCtx cxp = cx;
-            plan_lds(h, cxp, 1 << 30);
-            cxp.sc.n_lnodes = cxp.sc.n_lbtris = cxp.sc.n_ltri = 0;
+            plan_lds_no_walk(h, cxp);
             const long long chunk = std::min<long long>(n, launch_chunk(h, 25));
+            const int own = wave_owns_pixels(h, nsp, chunk);
             for (long long c0 = 0; c0 < n; c0 += chunk) {
                 const long long nc = std::min(chunk, n - c0);
                 ProbeBuffers pb;
-                const int probe_per_cu = big_launch_per_cu(h, nc);          // k_direct_probe 951 -> 879 us at 40 per CU on the C4 shard (profiles/r04_wf_grid_abk.txt)
-                if (int rc = probe_buffers(h, nc, 3, pb, s, probe_per_cu)) return rc;
-                const TraceQueue tq{pb.req, pb.count, pb.sub_cap};
-                const int blocks = (launch_blocks(h, nc, probe_per_cu) + kWfSub - 1) / kWfSub * kWfSub;
-                hipLaunchKernelGGL(k_direct_probe<FL>, dim3(blocks), dim3(kBlock), lds_bytes(cx, h), s, cx, tv0, o->spp, o->spp_begin, SlotDiv(nsp), c0, nc, tq, pb.hit, pb.mask,
-                                   make_rng_jump(o->rng_offset[0] + 2));
-                HIP_TRY(hipGetLastError());
-                if (int rc = launch_wf_trace(h, pb.req, pb.count, pb.sub_cap, pb.hit, s)) return rc;
+                if (int rc = probe_and_trace<FL>(h, o, cx, c0, nc, pb, s)) return rc;
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera<G, R, PSDR_INTEGRATOR_DIRECT, FL | kScenePre, false>), dim3(launch_blocks(h, nc, camera_blocks_per_cu(h, nc))), dim3(kBlock), cxp.off_stack, s,
                                    cxp, tvp, o->spp, o->spp_begin, SlotDiv(nsp), nc, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, c0, ProbeView{pb.hit, pb.mask}, own);
                 HIP_TRY(hipGetLastError());
@@ -1831,6 +1858,7 @@ int run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, 
             return 0;
         }
     }
+    const int own = wave_owns_pixels(h, nsp, n);          // k_camera `own`; these launches are not chunked
     // PathTracer, material tangents on albedo texels only, a variant without rough conductors / environment map: the log-derivative kernel and, behind the
     // same gate, the dual-number kernel (one of the two returns at once)
     bool gated = false;
@@ -2114,9 +2142,8 @@ template <int FL>
 int secondary_edge_filter(psdr_scene_s *h, const LaunchCtx &cx, long long i0, long long n, const uint32_t **list, const int **list_n, hipStream_t s, const GuideGrid *ggp = nullptr) {
     *list = nullptr; *list_n = nullptr;
     const GuideGrid gg = ggp ? *ggp : GuideGrid{0, 0, 0, 0, 0, 0.f};
-    const int split_env = h->opt.sedge_split;
-    if (!ggp && (split_env == 0 || (split_env < 0 && n < (1ll << 18)))) return 0;
     if (n > 0x7fffffffLL) return ggp ? fail("psdr_guide_build: more than 2^31 (stream, round) slots") : 0;
+    if (!ggp && !path_sedge_split(h, n)) return 0;
     const size_t need = 256 + (size_t) n * sizeof(uint32_t);
     if (int rc = scratch_reserve(&h->d_se_list, &h->se_list_bytes, need, s, "secondary-edge survivor list")) return rc;
     int *cnt = reinterpret_cast<int *>(h->d_se_list);
@@ -2126,8 +2153,7 @@ int secondary_edge_filter(psdr_scene_s *h, const LaunchCtx &cx, long long i0, lo
         if (traced_wavefront(h) && h->opt.probe != 0) {
             // traced launch: probe pass -> dense trace kernel -> the filter on primitives + hit rows (C4 shard: 12.2 ms as one kernel)
             LaunchCtx cxp = cx;
-            plan_lds(h, cxp, 1 << 30);
-            cxp.sc.n_lnodes = cxp.sc.n_lbtris = cxp.sc.n_ltri = 0;
+            plan_lds_no_walk(h, cxp);
             const long long chunk = std::min<long long>(n, launch_chunk(h, 25));
             for (long long c0 = 0; c0 < n; c0 += chunk) {
                 const long long nc = std::min(chunk, n - c0);
@@ -2177,9 +2203,7 @@ int render_fwd(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tangents *
     for (int k = 0; k < K; ++k) tv.t[k] = tangents[k];
     HIP_TRY(hipMemsetAsync(img, 0, sizeof(float) * WH * 3, s));
     HIP_TRY(hipMemsetAsync(dimg, 0, sizeof(float) * WH * 3 * K, s));
-    // geometry stays in plain fp32 when only material / emitter tables carry tangents
-    bool geo = false;
-    for (int k = 0; k < K; ++k) geo = geo || tangents[k].d_tri_info || tangents[k].d_cam_to_world;
+    const bool geo = tangents_move_geometry(tangents, K);
     if (geo && PSDR_TANGENT_LIVE && h->opt.tangent_live != 0) {
         static_assert(K <= 3, "TangentRows holds three sets");
         const int T = h->desc.num_tris;
@@ -2200,15 +2224,11 @@ int render_fwd(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tangents *
     else if (use_wavefront(h, o)) { if (int rc = run_camera_wavefront<Dual<K>, FL>(h, o, tv, img, dimg, s)) return rc; }
     else { if (int rc = run_camera<float, Dual<K>, FL>(h, o, tv, img, dimg, s)) return rc; }
     if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0) {
-        LaunchCtx cx;
-        if (int rc = make_ctx(h, o, 1, cx)) return rc;
-        const long long i0 = WH * o->sppe_begin, n = WH * (o->sppe_end - o->sppe_begin);
-        h->slots[1] += (uint64_t) n;
-        const uint32_t *order = nullptr;
-        if (int rc = primary_edge_order(h, cx, i0, n, &order, s)) return rc;
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
 #define PSDR_LAUNCH_PE(INTEG)                                                                                                        \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_primary_edge<K, FL, INTEG>), dim3(launch_blocks(h, n)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n,   \
-                           1.f / (float) o->sppe, dimg, WH * 3, h->d_counters, order)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_primary_edge<K, FL, INTEG>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, e.i0, e.n,   \
+                           1.f / (float) o->sppe, dimg, WH * 3, h->d_counters, e.order)
         switch (o->integrator) {
             case PSDR_INTEGRATOR_DIRECT: PSDR_LAUNCH_PE(PSDR_INTEGRATOR_DIRECT); break;
             case PSDR_INTEGRATOR_PATH: PSDR_LAUNCH_PE(PSDR_INTEGRATOR_PATH); break;
@@ -2218,36 +2238,15 @@ int render_fwd(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tangents *
         HIP_TRY(hipGetLastError());
     }
     if (o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0 && o->integrator == PSDR_INTEGRATOR_DIRECT) {
-        LaunchCtx cx;
-        if (int rc = make_ctx(h, o, 2, cx)) return rc;
-        const long long i0 = WH * o->sppse_begin, n = WH * (o->sppse_end - o->sppse_begin);
-        h->slots[2] += (uint64_t) n;
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
         const uint32_t *list = nullptr; const int *list_n = nullptr;
-        if (int rc = secondary_edge_filter<FL>(h, cx, i0, n, &list, &list_n, s)) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_secondary_edge<K, FL>), dim3(launch_blocks(h, list ? std::max(n / 16, 1ll << 16) : n)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n,
+        if (int rc = secondary_edge_filter<FL>(h, e.cx, e.i0, e.n, &list, &list_n, s)) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_secondary_edge<K, FL>), dim3(launch_blocks(h, list ? filter_grid_slots(e.n, 16) : e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, e.i0, e.n,
                            1.f / (float) o->sppse, dimg, WH * 3, h->d_counters, list, list_n);
         HIP_TRY(hipGetLastError());
     }
     return 0;
-}
-
-// Does the reverse launch of these camera slots with geometry gradients run its value sweep as the traced wavefront with recording stages (render_rev)?
-// Then psdr_render_c(PSDR_FLAG_KEEP_RECORDS) can BE that value sweep.  One rule, used by both.
-template <int FL> bool rev_value_sweep_is_wavefront(const psdr_scene_s *h, const psdr_render_opts *o, long long n) {
-    if constexpr ((FL & kSceneForest) == 0) return false;
-    if (o->integrator != PSDR_INTEGRATOR_PATH) return false;
-    const int depth = std::min(o->max_depth, kMaxRevDepthDeep);
-    const bool has_tree = h->num_nodes > 0 && (h->n_tiny == 0 || h->n_blas > 0);
-    const int split_env = h->opt.rev_split;
-    const bool split = split_env != 0 && (split_env == 1 || (has_tree && o->max_depth >= 2 && n >= (1ll << 20)));
-    return split && depth <= kMaxRevDepth && traced_wavefront(h) && use_wavefront(h, o);
-}
-inline bool same_camera_samples(const psdr_render_opts &a, const psdr_render_opts &b) {
-    return a.integrator == b.integrator && a.max_depth == b.max_depth && a.hide_emitters == b.hide_emitters && a.spp == b.spp && a.spp_begin == b.spp_begin &&
-           a.spp_end == b.spp_end && a.rng_offset[0] == b.rng_offset[0] && ((a.flags ^ b.flags) & (PSDR_FLAG_FUSED | PSDR_FLAG_WAVEFRONT)) == 0;
-}
-inline int rev_record_words(const psdr_scene_s *, int depth, bool wavefront) {
-    return kRevDiskHead + (wavefront ? kRevDiskPerVertexCf : kRevDiskPerVertex) * depth;
 }
 
 // value_only (psdr_render_c with PSDR_FLAG_KEEP_RECORDS where the traced wavefront does not apply -- a scene without a tree, a small launch): the PathTracer's
@@ -2259,111 +2258,39 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
     if (value_only) {
         const long long nv = WH * (o->spp_end - o->spp_begin);
         if (o->integrator != PSDR_INTEGRATOR_PATH || o->max_depth > kMaxRevDepth || o->max_depth < 1 || h->opt.rev_split == 0 || o->spp <= 0 || nv <= 0 ||
-            nv > launch_chunk(h, 26) || nv > fit_chunk(std::max(nv, 1ll << 18), (size_t) (kRevDiskHead + kRevDiskPerVertex * o->max_depth) * 4, 64u << 20, h->rev_bytes)) return 1;
+            nv > launch_chunk(h, 26) || nv > fit_chunk(std::max(nv, 1ll << 18), (size_t) rev_record_words(o->max_depth, false) * 4, 64u << 20, h->rev_bytes)) return 1;
     }
     if (out_img) HIP_TRY(hipMemsetAsync(out_img, 0, sizeof(float) * WH * 3, s));
-    DeviceSink<FL> sink{}; sink.g = *grads; sink.L = make_sink_layout(h, grads);
-    // the instances of scenes without a tree address a triangle's cached row directly (DeviceSink::add_tri): every row cached, slot == triangle
-    if ((FL & kSceneTiny) != 0 && PSDR_TINY_DIRECT_ROWS && grads->g_tri_info != nullptr && !(h->hot_identity && sink.L.hot_rows == h->desc.num_tris))
-        return fail("psdr_render_d_rev: the gradient cache of a scene without a tree does not hold every triangle row");
+    DeviceSink<FL> sink{};
+    if (int rc = make_device_sink(h, grads, sink)) return rc;
     const int nsp = o->spp_end - o->spp_begin;
     if (o->spp > 0 && nsp > 0) {
-        LaunchCtx cx;
+        LaunchCtx cx, cx2;
         if (int rc = make_ctx(h, o, 0, cx)) return rc;
+        const LaunchCtx cxf = cx;          // the probe pass of a probe launch stages the scene like a forward kernel
         const long long n = WH * nsp;
         h->slots[0] += (uint64_t) n;
-        const int depth = o->integrator == PSDR_INTEGRATOR_PATH ? std::min(o->max_depth, kMaxRevDepthDeep) : 1;
-        // up to kMaxRevDepth vertices the per-lane path record lives in LDS; deeper paths keep it in HBM, one column per thread of the grid
-        const bool deep_rec = depth > kMaxRevDepth;
-        const int rec_bytes = deep_rec ? 0 : depth * kPathRecWords * kBlock * 4;
+        // plan (psdr_plan.h): the launch form, the gradient cache's final layout, the LDS blocks of the kernels that walk the tree (cx) and of those that do not (cx2)
+        RevCameraPlan p;
+        if (int rc = plan_rev_camera(h, o, grads, n, FL, reg_priv_kernel<FL, true, PSDR_INTEGRATOR_PATH>(), value_only, out_img != nullptr, sink.L, cx, cx2, p)) return rc;
         float *deep = nullptr;
-        if (deep_rec) {
-            const size_t need = (size_t) launch_blocks(h, n) * kBlock * depth * kPathRecWords * sizeof(float);
+        if (p.deep_rec) {
+            const size_t need = (size_t) launch_blocks(h, n) * kBlock * p.depth * kPathRecWords * sizeof(float);
             if (int rc = scratch_reserve(&h->d_rev_deep, &h->rev_deep_bytes, need, s, "deep path records of the reverse launch")) return rc;
             deep = reinterpret_cast<float *>(h->d_rev_deep);
         }
-        const bool geo = value_only || grads->g_tri_info != nullptr || grads->g_cam_to_world != nullptr;
-        const int wg_per_cu = (o->integrator == PSDR_INTEGRATOR_DIRECT && !(FL & kSceneRough)) ? 3 : 2;       // rev_waves<FL, true, INTEG>
-        // Split launch: a scene with a tree to walk, geometry gradients (the register-heavy kernel), hits replayable.
-        const int split_env = h->opt.rev_split;
-        const bool replayable = o->integrator == PSDR_INTEGRATOR_PATH || (o->integrator == PSDR_INTEGRATOR_DIRECT && o->bsdf_samples <= 1 && o->light_samples <= 1);
-        const bool has_tree = h->num_nodes > 0 && (h->n_tiny == 0 || h->n_blas > 0);
-        // measured (tools/rev_split_probe.py, 4 M slots): PathTracer(3) cbox_bunny 6.8 -> 4.8 ms, bunny_light 5.6 -> 3.9, 50 k-triangle interior
-        // 11.4 -> 9.4, PathTracer(6) 21 -> 12 / 13 -> 7.3 / 36 -> 20; the DirectIntegrator (three rays per slot) only gains on the
-        // large tree (3.8 -> 3.3 ms; bunny scenes 2.0 -> 2.4); the 12-triangle box neither way
-        const bool worth = o->integrator == PSDR_INTEGRATOR_PATH ? o->max_depth >= 2 : h->num_nodes >= 16384;
-        // the records a recording psdr_render_c (value_only, above) left of exactly these samples on exactly these tables: this call is their adjoint kernel
-        const bool kept_fused = !value_only && geo && o->integrator == PSDR_INTEGRATOR_PATH && !deep_rec && split_env != 0 && h->kept.valid && h->kept.kind == 0 &&
-                                h->kept.gen == h->tables_gen && h->kept.n == n && out_img == nullptr && same_camera_samples(h->kept.o, *o) && n <= launch_chunk(h, 26);
-        const bool split = value_only || kept_fused || (geo && replayable && split_env != 0 && (split_env == 1 || (has_tree && worth && n >= (1ll << 20))));
-        // adjoint kernel of a split launch: nothing of the tree staged, no stacks -- only what plan_lds places without any room (the hit rows of
-        // the kernel-argument primitives and the small tables of the two-level / tiny instances, Tab<FL>::lds_small), then record and cache
-        // the PathTracer's geometry-adjoint kernels keep the lane-private emitter accumulators in registers (RegPrivSink): no LDS block, never switched off
-        sink.L.priv_regs = (geo && o->integrator == PSDR_INTEGRATOR_PATH && reg_priv_kernel<FL, true, PSDR_INTEGRATOR_PATH>()) ? 1 : 0;
-        LaunchCtx cx2 = cx;
-        plan_lds(h, cx2, 1 << 30);
-        const int base2 = cx2.off_stack;                           // bytes in front of where the stacks would start
-        cx2.sc.n_lnodes = cx2.sc.n_lbtris = cx2.sc.n_ltri = 0;
-        // lane-private emitter rows (30 KB) only where they do not cost a resident workgroup (C5 PathTracer(3) fused: stacks 22 KB +
-        // record 24 KB + cache 19 KB + 30 KB = one workgroup per CU instead of two, 11.5 -> 19.4 ms)
-        {
-            LaunchCtx probe = cx;
-            const int floor_bytes = (split ? base2 : plan_lds(h, probe, 1 << 30)) + rec_bytes;                  // (tables +) stacks only + record
-            if (!sink.L.priv_regs && sink.L.priv_rows > 0 && floor_bytes + sink_bytes(sink.L) > h->lds_limit / wg_per_cu) { sink.L.priv_rows = 0; sink.L.priv_emitter = -1; }
-        }
-        // deferred row adjoints (DeviceSink::defer_row -> sorted adds at the slot's end): one column per path vertex behind the primary one, where the
-        // block does not cost a resident workgroup
-        sink.L.pend_rows = 0; sink.L.pend_off = 0;
-        // (rows: measured on the PathTracer only -- C2 all gradients 5.28 -> 4.99 ms, the C4 shard's adjoint kernel 19.5 -> 18.7; the DirectIntegrator's
-        // single deferred row is level to 3 % slower: profiles/r05_rev_sorted_abk.txt)
-        if (geo && h->opt.rev_sorted != 0 && grads->g_tri_info != nullptr && o->integrator == PSDR_INTEGRATOR_PATH) {
-            LaunchCtx probe = cx;
-            const int floor_bytes = (split ? base2 : plan_lds(h, probe, 1 << 30)) + rec_bytes;
-            for (int rows = std::min(depth, 4); rows >= 1; --rows) {
-                SinkLayout t = sink.L;
-                sink_reserve_pending(t, rows);
-                if (floor_bytes + sink_bytes(t) <= h->lds_limit / wg_per_cu) { sink.L = t; break; }
-            }
-        }
-        const int cache_bytes = sink_bytes(sink.L);
-        {
-            int32_t *r = h->rev_layout;                                 // psdr_scene_rev_layout
-            r[0] = sink.L.tex_n; r[1] = sink.L.rad_n; r[2] = sink.L.env_n; r[3] = sink.L.hot_rows; r[4] = sink.L.rep;
-            r[5] = sink.L.priv_rows; r[6] = sink.L.priv_regs; r[7] = sink.L.pend_rows;
-            r[10] = h->hot_identity ? 1 : 0; r[11] = deep_rec ? 1 : 0; r[12] = sink.L.priv_slot[0]; r[13] = sink.L.priv_slot[1]; r[14] = h->hot_rows;
-        }
-        plan_lds(h, cx, split ? rec_bytes : rec_bytes + cache_bytes);   // stage less of the scene: the record (+ cache) live in LDS too
-        cx.off_pathrec = lds_bytes(cx, h);
-        cx.off_sink = cx.off_pathrec + rec_bytes;
-        cx2.off_stack = base2; cx2.off_pathrec = base2; cx2.off_sink = base2 + rec_bytes;
-        // a scene without a tree runs both kernels of a (forced) split launch on the layout of the fused one
-        const bool no_tree = lds_bytes(cx, h) == cx.off_stack;
-        if (split && no_tree) cx2 = cx;
-        const int dyn1 = cx.off_pathrec + rec_bytes;                   // value kernel of a split launch
-        const int dyn_bytes = (split && !no_tree) ? cx2.off_sink + cache_bytes : cx.off_sink + cache_bytes;
-        if (std::max(dyn_bytes, split ? dyn1 : 0) > h->lds_limit) return fail("psdr_render_d_rev: the launch needs " + std::to_string(dyn_bytes) + " bytes of LDS per workgroup (path record of " +
-                                                  std::to_string(depth) + " levels + traversal stacks + gradient cache), the device offers " + std::to_string(h->lds_limit));
+        const bool geo = p.geo, wf_value = p.form == kRevSplitWavefront;
         // material-only gradients (no triangle / camera table wanted) run the variant without the geometric adjoints;
         // the integrator is a compile-time parameter as in the forward kernels (direct: no path record / replay loop)
-#define PSDR_LAUNCH_REV_K(GEO, INTEG, STAGE, CX, BYTES, J0, N, IMG, DISK, STRIDE)                                                    \
-        do { if ((BYTES) > 48 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_camera_rev<FL, GEO, INTEG, STAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, (BYTES))); \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera_rev<FL, GEO, INTEG, STAGE>), dim3(launch_blocks(h, (N))), dim3(kBlock), (BYTES), s, CX, sink, \
-                           o->spp, o->spp_begin, nsp, (long long) (J0), (long long) (N), 1.f / (float) o->spp, adj_img, IMG, h->d_counters, DISK, (long long) (STRIDE), deep, disk_cf, ProbeView{nullptr, nullptr}); } while (0)
-#define PSDR_LAUNCH_REV(GEO, INTEG) PSDR_LAUNCH_REV_K(GEO, INTEG, 0, cx, dyn_bytes, 0, n, out_img, (float *) nullptr, 0)
-        // the value sweep of a split PathTracer launch on a two-level scene runs as the TRACED WAVEFRONT (dense trace kernel between the stages):
-        // in the fused value kernel a wave pays its slowest lane's tree walk at every closest_hit (C4 shard: 29 ms of the 57; renderC by the
-        // wavefront: 16 ms)
-        bool wf_value = false;
-        if constexpr ((FL & kSceneForest) != 0) wf_value = split && !value_only && !kept_fused && !no_tree && o->integrator == PSDR_INTEGRATOR_PATH && !deep_rec && traced_wavefront(h) && use_wavefront(h, o);
-        // (rev_value_sweep_is_wavefront states the same rule for psdr_render_c's PSDR_FLAG_KEEP_RECORDS; `geo` and the option rev_split == 1 on a scene
-        // without a tree are the caller's side of it)
-        const int disk_cf = wf_value ? 1 : 0;
-        bool direct_probe = false;
-        if constexpr ((FL & kSceneForest) != 0) direct_probe = !split && !no_tree && o->integrator == PSDR_INTEGRATOR_DIRECT && probe_direct(h, o, n);
-        h->rev_layout[8] = split ? (wf_value ? 2 : 1) : direct_probe ? 4 : 0;
-        if (split) {
-            // records of one chunk of slots live in a scratch buffer (2 + 5 depth words per slot; 2 + 8 depth from the wavefront); chunks bound its size
-            const int words = kRevDiskHead + (wf_value ? kRevDiskPerVertexCf : kRevDiskPerVertex) * depth;
+#define PSDR_LAUNCH_REV_K(FLAGS, GEO, INTEG, STAGE, CX, SINK, BYTES, J0, N, IMG, DISK, STRIDE, PROBE)                                  \
+        do { if (int rc = allow_dynamic_lds(&k_camera_rev<FLAGS, GEO, INTEG, STAGE>, (BYTES))) return rc;                               \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera_rev<FLAGS, GEO, INTEG, STAGE>), dim3(launch_blocks(h, (N))), dim3(kBlock), (BYTES), s, CX, SINK, \
+                           o->spp, o->spp_begin, nsp, (long long) (J0), (long long) (N), 1.f / (float) o->spp, adj_img, IMG, h->d_counters, DISK, (long long) (STRIDE), deep, wf_value ? 1 : 0, PROBE); } while (0)
+#define PSDR_LAUNCH_REV(GEO, INTEG) PSDR_LAUNCH_REV_K(FL, GEO, INTEG, 0, cx, sink, p.dyn_bytes, 0, n, out_img, (float *) nullptr, 0, (ProbeView{nullptr, nullptr}))
+#define PSDR_LAUNCH_REV_S(INTEG, STAGE, CX, BYTES, IMG) PSDR_LAUNCH_REV_K(FL, true, INTEG, STAGE, CX, sink, BYTES, c0, nc, IMG, disk, chunk, (ProbeView{nullptr, nullptr}))
+        if (p.split) {
+            // records of one chunk of slots live in a scratch buffer (rev_record_words per slot); chunks bound its size
+            const int words = rev_record_words(p.depth, wf_value);
             // (kept records of exactly this launch on the handle: the buffer exists and holds them -- no sizing against the free memory)
             const bool reuse_possible = h->kept.valid && h->kept.gen == h->tables_gen && h->kept.n == n && (size_t) n * words * sizeof(float) <= h->rev_bytes;
             // 2^26 slots per chunk (104 B of records per slot with the wavefront's cf format: 7 GB): the C4 shard's PathTracer(3) reverse as ONE chunk
@@ -2374,10 +2301,10 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
             if (int rc = scratch_reserve(&h->d_rev, &h->rev_bytes, need, s, "per-path records of the split reverse launch")) return rc;
             float *disk = reinterpret_cast<float *>(h->d_rev);
             // the records psdr_render_c(PSDR_FLAG_KEEP_RECORDS) left of exactly these samples on exactly these tables: the value sweep is already there
-            const bool reuse = (wf_value ? h->kept.kind == 1 : kept_fused) && h->kept.valid && h->kept.gen == h->tables_gen && h->kept.n == n && chunk >= n && out_img == nullptr &&
+            const bool reuse = (wf_value ? h->kept.kind == 1 : p.kept_fused) && h->kept.valid && h->kept.gen == h->tables_gen && h->kept.n == n && chunk >= n && out_img == nullptr &&
                                same_camera_samples(h->kept.o, *o) && need <= h->rev_bytes;
             if (!reuse) h->kept.valid = false;          // this launch overwrites them
-            else h->rev_layout[8] = 3;
+            else h->rev_layout[8] = kRevKeptRecords;
             for (long long c0 = 0; c0 < n; c0 += chunk) {
                 const long long nc = std::min(chunk, n - c0);
                 if (o->integrator == PSDR_INTEGRATOR_PATH) {
@@ -2390,49 +2317,31 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
                             if (int rc = run_camera_wavefront<float, FL>(h, o, tv0, out_img, nullptr, s, &ra)) return rc;
                         }
                     } else
-                    PSDR_LAUNCH_REV_K(true, PSDR_INTEGRATOR_PATH, 1, cx, dyn1, c0, nc, out_img, disk, chunk);
+                    PSDR_LAUNCH_REV_S(PSDR_INTEGRATOR_PATH, 1, cx, p.dyn1, out_img);
                     if (value_only) {
                         HIP_TRY(hipGetLastError());
                         h->kept.valid = true; h->kept.o = *o; h->kept.gen = h->tables_gen; h->kept.n = n; h->kept.kind = 0;
                         return 0;
                     }
-                    PSDR_LAUNCH_REV_K(true, PSDR_INTEGRATOR_PATH, 2, cx2, dyn_bytes, c0, nc, (float *) nullptr, disk, chunk);
+                    PSDR_LAUNCH_REV_S(PSDR_INTEGRATOR_PATH, 2, cx2, p.dyn_bytes, (float *) nullptr);
                 } else {
-                    PSDR_LAUNCH_REV_K(true, PSDR_INTEGRATOR_DIRECT, 1, cx, dyn1, c0, nc, out_img, disk, chunk);
-                    PSDR_LAUNCH_REV_K(true, PSDR_INTEGRATOR_DIRECT, 2, cx2, dyn_bytes, c0, nc, (float *) nullptr, disk, chunk);
+                    PSDR_LAUNCH_REV_S(PSDR_INTEGRATOR_DIRECT, 1, cx, p.dyn1, out_img);
+                    PSDR_LAUNCH_REV_S(PSDR_INTEGRATOR_DIRECT, 2, cx2, p.dyn_bytes, (float *) nullptr);
                 }
             }
             // kept records are ONE-SHOT: the reverse call that consumed them clears them (a caller who rewrites tables in place under an unchanged descriptor and a
             // repeated rng_offset must not meet the records of the old tables: ADVICE r5); the Python surface renders a recording primal before every backward
             h->kept.valid = false;
-        } else if (direct_probe) {
+        } else if (p.form == kRevProbe) {
             if constexpr ((FL & kSceneForest) != 0) {
-                // DirectIntegrator(1, 1), one kernel, on a two-level scene: probe pass -> dense trace kernel -> the reverse kernel on primitives + hit rows
-                const TangentView<0, FL> tv0{};
+                // probe pass -> dense trace kernel -> the reverse kernel on primitives + hit rows (cx2: record + cache, nothing of the tree, no stacks)
                 DeviceSink<FL | kScenePre> sinkp{}; sinkp.g = sink.g; sinkp.L = sink.L;
-                LaunchCtx cxf;
-                if (int rc = make_ctx(h, o, 0, cxf)) return rc;                                   // the probe pass stages the scene like a forward kernel
-                LaunchCtx cxp = cx;                                                              // the final pass: record + cache, nothing of the tree, no stacks
-                plan_lds(h, cxp, 1 << 30);
-                cxp.sc.n_lnodes = cxp.sc.n_lbtris = cxp.sc.n_ltri = 0;
-                cxp.off_pathrec = cxp.off_stack; cxp.off_sink = cxp.off_pathrec + rec_bytes;
-                const int dyn_p = cxp.off_sink + cache_bytes;
                 const long long chunk = std::min<long long>(n, launch_chunk(h, 25));
                 for (long long c0 = 0; c0 < n; c0 += chunk) {
                     const long long nc = std::min(chunk, n - c0);
                     ProbeBuffers pb;
-                    const int probe_per_cu = big_launch_per_cu(h, nc);
-                    if (int rc = probe_buffers(h, nc, 3, pb, s, probe_per_cu)) return rc;
-                    const TraceQueue tq{pb.req, pb.count, pb.sub_cap};
-                    const int blocks = (launch_blocks(h, nc, probe_per_cu) + kWfSub - 1) / kWfSub * kWfSub;
-                    hipLaunchKernelGGL(k_direct_probe<FL>, dim3(blocks), dim3(kBlock), lds_bytes(cxf, h), s, cxf, tv0, o->spp, o->spp_begin, SlotDiv(nsp), c0, nc, tq, pb.hit, pb.mask,
-                                       make_rng_jump(o->rng_offset[0] + 2));
-                    HIP_TRY(hipGetLastError());
-                    if (int rc = launch_wf_trace(h, pb.req, pb.count, pb.sub_cap, pb.hit, s)) return rc;
-#define PSDR_LAUNCH_REV_P(GEO)                                                                                                            \
-                    do { if (dyn_p > 48 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_camera_rev<FL | kScenePre, GEO, PSDR_INTEGRATOR_DIRECT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_p)); \
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera_rev<FL | kScenePre, GEO, PSDR_INTEGRATOR_DIRECT, 0>), dim3(launch_blocks(h, nc)), dim3(kBlock), dyn_p, s, cxp, sinkp,  \
-                                       o->spp, o->spp_begin, nsp, c0, nc, 1.f / (float) o->spp, adj_img, out_img, h->d_counters, (float *) nullptr, 0ll, deep, 0, ProbeView{pb.hit, pb.mask}); } while (0)
+                    if (int rc = probe_and_trace<FL>(h, o, cxf, c0, nc, pb, s)) return rc;
+#define PSDR_LAUNCH_REV_P(GEO) PSDR_LAUNCH_REV_K(FL | kScenePre, GEO, PSDR_INTEGRATOR_DIRECT, 0, cx2, sinkp, p.dyn_bytes, c0, nc, out_img, (float *) nullptr, 0, (ProbeView{pb.hit, pb.mask}))
                     if (geo) PSDR_LAUNCH_REV_P(true); else PSDR_LAUNCH_REV_P(false);
 #undef PSDR_LAUNCH_REV_P
                     HIP_TRY(hipGetLastError());
@@ -2446,30 +2355,17 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
         }
 #undef PSDR_LAUNCH_REV_K
 #undef PSDR_LAUNCH_REV
+#undef PSDR_LAUNCH_REV_S
         HIP_TRY(hipGetLastError());
     }
     if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0 && grads->g_prim_edge) {
-        LaunchCtx cx;
-        if (int rc = make_ctx(h, o, 1, cx)) return rc;
-        const long long i0 = WH * o->sppe_begin, n = WH * (o->sppe_end - o->sppe_begin);
-        h->slots[1] += (uint64_t) n;
-        // replicated gradient table (see PrimaryEdgeSink): up to 64 copies within 64 MB of the sort scratch's neighbour buffer
-        const long long pe_words = (long long) h->desc.num_prim_edges * PSDR_PEDGE_STRIDE;
-        int reps = 1;
-        while (reps < 64 && (long long) (reps * 2) * pe_words * 4 <= (64ll << 20)) reps *= 2;
-        if (n < (1ll << 18)) reps = 1;
-        if (reps > 1) {
-            const size_t need = (size_t) reps * pe_words * sizeof(float);
-            if (int rc = scratch_reserve(&h->d_pe_rep, &h->pe_rep_bytes, need, s, "primary-edge gradient replicas")) return rc;
-            HIP_TRY(hipMemsetAsync(h->d_pe_rep, 0, need, s));
-        }
-        const PrimaryEdgeSink<FL> pe_sink{reps > 1 ? reinterpret_cast<float *>(h->d_pe_rep) : grads->g_prim_edge, pe_words, reps};
-        const uint32_t *order = nullptr;
-        if (int rc = primary_edge_order(h, cx, i0, n, &order, s)) return rc;
-        h->rev_layout[9] = reps; h->rev_layout[15] = order != nullptr ? 1 : 0;
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
+        PrimaryEdgeSink<FL> pe_sink;
+        if (int rc = begin_pe_replicas(h, grads, e, pe_sink, s)) return rc;
 #define PSDR_LAUNCH_PER(INTEG)                                                                                                       \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_primary_edge_rev<FL, INTEG>), dim3(launch_blocks(h, n, big_launch_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, pe_sink, i0, n, \
-                           1.f / (float) o->sppe, adj_img, h->d_counters, order)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_primary_edge_rev<FL, INTEG>), dim3(launch_blocks(h, e.n, big_launch_per_cu(h, e.n))), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, pe_sink, e.i0, e.n, \
+                           1.f / (float) o->sppe, adj_img, h->d_counters, e.order)
         switch (o->integrator) {
             case PSDR_INTEGRATOR_DIRECT: PSDR_LAUNCH_PER(PSDR_INTEGRATOR_DIRECT); break;
             case PSDR_INTEGRATOR_PATH: PSDR_LAUNCH_PER(PSDR_INTEGRATOR_PATH); break;
@@ -2477,32 +2373,18 @@ int render_rev_impl(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
         }
 #undef PSDR_LAUNCH_PER
         HIP_TRY(hipGetLastError());
-        if (reps > 1) {
-            hipLaunchKernelGGL(k_sum_replicas, dim3((unsigned) ((pe_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, grads->g_prim_edge,
-                               reinterpret_cast<const float *>(h->d_pe_rep), pe_words, reps);
-            HIP_TRY(hipGetLastError());
-        }
+        if (int rc = end_pe_replicas(h, grads, pe_sink, s)) return rc;
     }
     if (o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0 && o->integrator == PSDR_INTEGRATOR_DIRECT) {
-        LaunchCtx cx;
-        if (int rc = make_ctx(h, o, 2, cx)) return rc;
-        const long long i0 = WH * o->sppse_begin, n = WH * (o->sppse_end - o->sppse_begin);
-        h->slots[2] += (uint64_t) n;
-        sink.L.priv_rows = 0; sink.L.priv_emitter = -1;            // boundary samples land on the emitter once per slot: no private rows
-        sink.L.pend_rows = 0; sink.L.pend_off = 0;                 // (nothing deferred in this kernel)
-        const int cache_bytes = sink_bytes(sink.L);
-        plan_lds(h, cx, cache_bytes);
-        cx.off_sink = lds_bytes(cx, h);
-        const int dyn_bytes = cx.off_sink + cache_bytes;
-        if (dyn_bytes > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_secondary_edge_rev<FL>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes));
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
+        const LaunchCtx cxf = e.cx;                                 // the filter stages the scene like a forward kernel (no gradient cache in LDS)
+        int dyn_bytes = 0;
+        if (int rc = plan_rev_one_vertex(h, e.cx, sink.L, &dyn_bytes)) return rc;
+        if (int rc = allow_dynamic_lds(&k_secondary_edge_rev<FL>, dyn_bytes)) return rc;
         const uint32_t *list = nullptr; const int *list_n = nullptr;
-        {
-            LaunchCtx cxf;                                          // the filter stages the scene like a forward kernel (no gradient cache in LDS)
-            if (int rc = make_ctx(h, o, 2, cxf)) return rc;
-            if (int rc = secondary_edge_filter<FL>(h, cxf, i0, n, &list, &list_n, s)) return rc;
-        }
-        hipLaunchKernelGGL(k_secondary_edge_rev<FL>, dim3(launch_blocks(h, list ? std::max(n / 16, 1ll << 16) : n)), dim3(kBlock), dyn_bytes, s, cx, sink, i0, n, 1.f / (float) o->sppse,
+        if (int rc = secondary_edge_filter<FL>(h, cxf, e.i0, e.n, &list, &list_n, s)) return rc;
+        hipLaunchKernelGGL(k_secondary_edge_rev<FL>, dim3(launch_blocks(h, list ? filter_grid_slots(e.n, 16) : e.n)), dim3(kBlock), dyn_bytes, s, e.cx, sink, e.i0, e.n, 1.f / (float) o->sppse,
                            adj_img, h->d_counters, list, list_n);
         HIP_TRY(hipGetLastError());
     }
@@ -2519,7 +2401,7 @@ int guide_launch(psdr_scene_s *h, LaunchCtx &cx, const int32_t reso[4], int nrou
             const GuideGrid gg{reso[0], reso[1], reso[2], reso[3], (int) n, 1.f / ((float) reso[3] * (float) nrounds)};
             const uint32_t *list = nullptr; const int *list_n = nullptr;
             if (int rc = secondary_edge_filter<FL>(h, cx, 0, n * nrounds, &list, &list_n, s, &gg)) return rc;
-            hipLaunchKernelGGL(k_guide_survivors<FL>, dim3(launch_blocks(h, std::max(n * nrounds / 16, 1ll << 16))), dim3(kBlock), lds_bytes(cx, h), s, cx, gg, list, list_n, out_mass, h->d_counters);
+            hipLaunchKernelGGL(k_guide_survivors<FL>, dim3(launch_blocks(h, filter_grid_slots(n * nrounds, 16))), dim3(kBlock), lds_bytes(cx, h), s, cx, gg, list, list_n, out_mass, h->d_counters);
             HIP_TRY(hipGetLastError());
             return 0;
         }
@@ -2543,11 +2425,10 @@ int render_c_launch(psdr_scene_s *h, const psdr_render_opts *o, float *out_img, 
         const long long n = (long long) h->desc.width * h->desc.height * (o->spp_end - o->spp_begin);
         // (records + streams of the whole launch must fit the device NOW -- 104 + ~230 bytes per slot; otherwise the plain render below, and the reverse call runs its own,
         // chunked value sweep: no failure for want of memory)
-        const int depth_k = std::min(o->max_depth, kMaxRevDepthDeep);
-        if ((o->flags & PSDR_FLAG_KEEP_RECORDS) != 0 && h->opt.keep_records != 0 && o->spp > 0 && n > 0 && n <= launch_chunk(h, 26) && rev_value_sweep_is_wavefront<FL>(h, o, n) &&
-            n <= fit_chunk(std::max(n, 1ll << 18), (size_t) rev_record_words(h, depth_k, true) * 4 + 240, 128u << 20, h->rev_bytes + h->ws_bytes)) {
-            const int depth = depth_k;
-            const size_t need = (size_t) n * rev_record_words(h, depth, true) * sizeof(float);
+        const int depth = std::min(o->max_depth, kMaxRevDepthDeep);
+        if ((o->flags & PSDR_FLAG_KEEP_RECORDS) != 0 && h->opt.keep_records != 0 && o->spp > 0 && n > 0 && n <= launch_chunk(h, 26) && rev_value_sweep_is_wavefront(h, o, n) &&
+            n <= fit_chunk(std::max(n, 1ll << 18), (size_t) rev_record_words(depth, true) * 4 + 240, 128u << 20, h->rev_bytes + h->ws_bytes)) {
+            const size_t need = (size_t) n * rev_record_words(depth, true) * sizeof(float);
             h->kept.valid = false;
             if (int rc = scratch_reserve(&h->d_rev, &h->rev_bytes, need, s, "per-path records of the split reverse launch")) return rc;
             const WfRecArgs ra{reinterpret_cast<float *>(h->d_rev), n, 0, n};

@@ -88,7 +88,7 @@ int logd_lean_launch_8(psdr_scene_s *h, const psdr_render_opts *o, const LaunchC
     const long long WH = (long long) h->desc.width * h->desc.height;
     const int nsp = o->spp_end - o->spp_begin;
     const long long n = WH * nsp;
-    const int own = (h->opt.own_pixels != 0 && nsp <= 64 && 64 % nsp == 0) ? 1 : 0;
+    const int own = wave_owns_pixels(h, nsp, n);
     const dim3 grid(launch_blocks(h, n, camera_blocks_per_cu(h, n)));
     const ulonglong2 *seed = seed_table(h, o, WH, nsp, n, s);
     if (seed != nullptr)

@@ -160,10 +160,6 @@ __global__ __launch_bounds__(kBlock) void k_path_sedge_rev(LaunchCtx cx, DeviceS
 inline bool path_sedges_wanted(const psdr_scene_s *h, const psdr_render_opts *o) {
     return o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0 && o->integrator == PSDR_INTEGRATOR_PATH && (o->flags & PSDR_FLAG_PATH_SEDGES) != 0;
 }
-inline bool path_sedge_split(const psdr_scene_s *h, long long n) {          // the rule of secondary_edge_filter
-    const int split_env = h->opt.sedge_split;
-    return !(split_env == 0 || (split_env < 0 && n < (1ll << 18))) && n <= 0x7fffffffLL;
-}
 inline PathGuide path_guide_of(const psdr_scene_s *h) {
     PathGuide g;
     g.cmf = h->pg_cmf; g.pmf = h->pg_pmf; g.sum = h->pg_sum;
@@ -200,14 +196,14 @@ int path_sedge_passes(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCt
         const uint32_t *list = nullptr; const int *list_n = nullptr;
         if (int rc = secondary_edge_filter<FL>(h, cxf, i0, n, &list, &list_n, s)) return rc;
         PathSedgeOpts pa = po; pa.seg = 1;
-        launch(list, list_n, list ? std::max(n / 16, 1ll << 16) : n, pa, ga);
+        launch(list, list_n, list ? filter_grid_slots(n, 16) : n, pa, ga);
         HIP_TRY(hipGetLastError());
     }
     if (po.seg & 2) {
         const uint32_t *list = nullptr; const int *list_n = nullptr;
         if (int rc = path_sedge_filter_b<FL>(h, cxf, i0, n, &list, &list_n, s, po.gb)) return rc;
         PathSedgeOpts pb = po; pb.seg = 2;
-        launch(list, list_n, std::max(n / 4, 1ll << 16), pb, gb);
+        launch(list, list_n, filter_grid_slots(n, 4), pb, gb);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -218,16 +214,14 @@ int path_sedge_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tang
     const long long WH = (long long) h->desc.width * h->desc.height;
     TangentView<K, FL> tv;
     for (int k = 0; k < K; ++k) tv.t[k] = tangents[k];
-    LaunchCtx cx;
-    if (int rc = make_ctx(h, o, 2, cx)) return rc;
-    const long long i0 = WH * o->sppse_begin, n = WH * (o->sppse_end - o->sppse_begin);
-    h->slots[2] += (uint64_t) n;
-    return path_sedge_passes<FL>(h, o, cx, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po, bool guided) {
+    EdgeLaunch e;
+    if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
+    return path_sedge_passes<FL>(h, o, e.cx, e.i0, e.n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po, bool guided) {
         if (guided)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL, true>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppse,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL, true>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, e.i0, e.n, 1.f / (float) o->sppse,
                                dimg, WH * 3, h->d_counters, list, list_n, PathSedgeArgs<true>{po.max_depth, po.seg, po.walk, po.gb});
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL, false>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, i0, n, 1.f / (float) o->sppse,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge<K, FL, false>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, e.i0, e.n, 1.f / (float) o->sppse,
                                dimg, WH * 3, h->d_counters, list, list_n, PathSedgeArgs<false>{po.max_depth, po.seg, po.walk});
     });
 }
@@ -241,33 +235,21 @@ int path_sedge_fwd(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr
 template <int FL>
 int path_sedge_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, hipStream_t s) {
     if (!path_sedges_wanted(h, o)) return 0;
-    const long long WH = (long long) h->desc.width * h->desc.height;
-    DeviceSink<FL> sink{}; sink.g = *grads; sink.L = make_sink_layout(h, grads);
-    if ((FL & kSceneTiny) != 0 && PSDR_TINY_DIRECT_ROWS && grads->g_tri_info != nullptr && !(h->hot_identity && sink.L.hot_rows == h->desc.num_tris))
-        return fail("psdr_render_d_rev: the gradient cache of a scene without a tree does not hold every triangle row");
-    LaunchCtx cx;
-    if (int rc = make_ctx(h, o, 2, cx)) return rc;
-    const long long i0 = WH * o->sppse_begin, n = WH * (o->sppse_end - o->sppse_begin);
-    h->slots[2] += (uint64_t) n;
-    sink.L.priv_rows = 0; sink.L.priv_emitter = -1; sink.L.priv_regs = 0;          // as the DirectIntegrator's secondary-edge kernel: no private rows, nothing deferred
-    sink.L.pend_rows = 0; sink.L.pend_off = 0;
-    const int cache_bytes = sink_bytes(sink.L);
-    plan_lds(h, cx, cache_bytes);
-    cx.off_sink = lds_bytes(cx, h);
-    const int dyn_bytes = cx.off_sink + cache_bytes;
-    if (dyn_bytes > h->lds_limit) return fail("psdr_render_d_rev: the secondary-edge launch needs " + std::to_string(dyn_bytes) + " bytes of LDS per workgroup");
-    if (dyn_bytes > 48 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_path_sedge_rev<FL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_path_sedge_rev<FL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_bytes));
-    }
-    LaunchCtx cxf;                                              // the filters stage the scene like a forward kernel (no gradient cache in LDS)
-    if (int rc = make_ctx(h, o, 2, cxf)) return rc;
-    return path_sedge_passes<FL>(h, o, cxf, i0, n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po, bool guided) {
+    DeviceSink<FL> sink{};
+    if (int rc = make_device_sink(h, grads, sink)) return rc;
+    EdgeLaunch e;
+    if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
+    const LaunchCtx cxf = e.cx;                                 // the filters stage the scene like a forward kernel (no gradient cache in LDS)
+    int dyn_bytes = 0;
+    if (int rc = plan_rev_one_vertex(h, e.cx, sink.L, &dyn_bytes)) return rc;
+    if (int rc = allow_dynamic_lds(&k_path_sedge_rev<FL, false>, dyn_bytes)) return rc;
+    if (int rc = allow_dynamic_lds(&k_path_sedge_rev<FL, true>, dyn_bytes)) return rc;
+    return path_sedge_passes<FL>(h, o, cxf, e.i0, e.n, s, [&](const uint32_t *list, const int *list_n, long long grid_slots, const PathSedgeOpts &po, bool guided) {
         if (guided)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge_rev<FL, true>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, cx, sink, i0, n, 1.f / (float) o->sppse, adj_img,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge_rev<FL, true>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, e.cx, sink, e.i0, e.n, 1.f / (float) o->sppse, adj_img,
                                h->d_counters, list, list_n, PathSedgeArgs<true>{po.max_depth, po.seg, po.walk, po.gb});
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge_rev<FL, false>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, cx, sink, i0, n, 1.f / (float) o->sppse, adj_img,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_sedge_rev<FL, false>), dim3(launch_blocks(h, grid_slots)), dim3(kBlock), dyn_bytes, s, e.cx, sink, e.i0, e.n, 1.f / (float) o->sppse, adj_img,
                                h->d_counters, list, list_n, PathSedgeArgs<false>{po.max_depth, po.seg, po.walk});
     });
 }
@@ -286,10 +268,10 @@ int path_guide_build(psdr_scene_s *h, const psdr_render_opts *o, int segment, co
     if (path_sedge_split(h, total)) {
         if (segment == 1) {
             if (int rc = secondary_edge_filter<FL>(h, cx, 0, total, &list, &list_n, s, &gg)) return rc;
-            grid_slots = std::max(total / 16, 1ll << 16);
+            grid_slots = filter_grid_slots(total, 16);
         } else {
             if (int rc = path_sedge_filter_b<FL>(h, cx, 0, total, &list, &list_n, s, PathGuide{}, &gg)) return rc;
-            grid_slots = std::max(total / 4, 1ll << 16);
+            grid_slots = filter_grid_slots(total, 4);
         }
     }
     hipLaunchKernelGGL(k_path_guide<FL>, dim3(launch_blocks(h, grid_slots)), dim3(kBlock), lds_bytes(cx, h), s, cx, gg, total, po, out_mass, h->d_counters, list, list_n);
