@@ -38,6 +38,7 @@ def load_oracle():
     L.psdr_oracle_trace.argtypes = [C.POINTER(SceneDesc), i32] + [vp] * 7 + [vp] * 4
     L.psdr_oracle_render.argtypes = [C.POINTER(SceneDesc), C.POINTER(RenderOpts), i32, C.POINTER(Tangents), vp, vp,
                                      i32, i32]
+    L.psdr_oracle_render_f64.argtypes = [C.POINTER(SceneDesc), C.POINTER(RenderOpts), i32, C.POINTER(Tangents), vp, vp, i32]
     L.psdr_oracle_guide_build.argtypes = [C.POINTER(SceneDesc), C.POINTER(RenderOpts), C.POINTER(i32), i32, vp, i32]
     L.psdr_oracle_rng.argtypes = [C.c_uint64, C.c_uint64, i32, vp]
     L.psdr_oracle_pcg32_raw.argtypes = [C.c_uint64, C.c_uint64, i32, vp]
@@ -61,12 +62,13 @@ def _cpu_tables(tb):
     return {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in tb.items()}
 
 
-def render(tb, opts, mode=0, tangents=None, guide=None, precision=0, nthreads=None, reference_form=False):
+def render(tb, opts, mode=0, tangents=None, guide=None, precision=0, nthreads=None, reference_form=False, out64=False):
     """mode 0: renderC -> img [H*W,3]; mode 1: renderD forward -> (img, dimg).
     tangents: dict name -> tensor (names of _abi.TANGENT_FIELDS).
     reference_form: evaluate the reference's literal expressions (p = ray(t) for the solid-angle hit, edge rays that
     may re-hit the faces adjacent to their edge) instead of the fp32-robust forms the product uses; identical in
-    exact arithmetic (psdr_oracle.cpp g_reference_form)."""
+    exact arithmetic (psdr_oracle.cpp g_reference_form).
+    out64 (with precision=1): the images as float64 arrays, not rounded to float (psdr_oracle_render_f64)."""
     L = lib()
     L.psdr_oracle_set_reference_form(1 if reference_form else 0)
     tb = _cpu_tables(tb)
@@ -84,6 +86,13 @@ def render(tb, opts, mode=0, tangents=None, guide=None, precision=0, nthreads=No
                 keep.append(t)
                 setattr(tan, "d_" + name, t.data_ptr())
     nthreads = nthreads or os.cpu_count() or 1
+    if out64:
+        assert precision == 1, "out64 is the fp64 oracle's output"
+        img, dimg = img.astype(np.float64), dimg.astype(np.float64)
+        rc = L.psdr_oracle_render_f64(C.byref(desc), C.byref(opts), mode, C.byref(tan), img.ctypes.data, dimg.ctypes.data if mode else None, nthreads)
+        if rc:
+            raise RuntimeError(L.psdr_oracle_last_error().decode())
+        return (img.reshape(-1, 3), dimg.reshape(-1, 3)) if mode else img.reshape(-1, 3)
     rc = L.psdr_oracle_render(C.byref(desc), C.byref(opts), mode, C.byref(tan), img.ctypes.data,
                               dimg.ctypes.data if mode else None, precision, nthreads)
     if rc:

@@ -2,27 +2,11 @@
 kernels, derivative w.r.t. texels (forward) and per-texel gradient scatter-add (reverse)."""
 import numpy as np
 import pytest
-import torch
 
 import oracle
-import psdr_cuda
-from enoki.cuda_autodiff import Vector3f as Vector3fD
 from helpers import GpuScene, dot_tables, host_render, host_render_rev, random_tangents, rel_l2
 from psdr_cuda import _abi
-from psdr_cuda.fixtures import scene_path
-
-
-def textured_scene(res=24, spp=8):
-    sc = psdr_cuda.Scene()
-    sc.load_file(scene_path("cbox_uv"), False)
-    sc.opts.width = sc.opts.height = res
-    sc.opts.spp, sc.opts.sppe, sc.opts.sppse, sc.opts.log_level = spp, 0, 0, 0
-    g = torch.Generator().manual_seed(7)
-    w, h = 6, 5
-    data = torch.rand(w * h, 3, generator=g) * 0.8 + 0.1
-    sc.param_map["BSDF[id=floor_tex]"].reflectance = psdr_cuda.Bitmap3fD(w, h, Vector3fD(data))
-    sc.configure()
-    return sc
+from texture_cases import rough_textured_scene, textured_scene
 
 
 def test_tables_carry_uv_and_texture():
@@ -77,31 +61,6 @@ def test_textured_render_gpu():
     _, grads = g.render_d_rev(o, adj, want=["texels"], with_image=False)
     lhs, rhs = float((adj.astype(np.float64) * dimg[0]).sum()), dot_tables(grads, tan)
     assert abs(lhs - rhs) < 1e-3 * np.abs(adj * dimg[0]).sum()
-
-
-def rough_textured_scene(res=24, spp=8):
-    """the uv-mapped floor as a rough conductor whose alpha_u / alpha_v / eta / k / specular reflectance are ALL
-    bitmaps of different resolutions (roughconductor.cpp:40-92 does five texture lookups per call)"""
-    from enoki.cuda_autodiff import Float32 as FloatD
-    sc = psdr_cuda.Scene()
-    sc.load_file(scene_path("cbox_uv"), False)
-    sc.opts.width = sc.opts.height = res
-    sc.opts.spp, sc.opts.sppe, sc.opts.sppse, sc.opts.log_level = spp, 0, 0, 0
-    g = torch.Generator().manual_seed(11)
-    metal = psdr_cuda.RoughConductor(0.2, (0.2, 0.9, 1.1), (3.9, 2.4, 2.2))
-    metal.alpha_u = psdr_cuda.Bitmap1fD(4, 3, FloatD(torch.rand(12, generator=g) * 0.3 + 0.08))
-    metal.alpha_v = psdr_cuda.Bitmap1fD(2, 5, FloatD(torch.rand(10, generator=g) * 0.3 + 0.08))
-    metal.eta = psdr_cuda.Bitmap3fD(3, 3, Vector3fD(torch.rand(9, 3, generator=g) * 1.0 + 0.2))
-    metal.k = psdr_cuda.Bitmap3fD(2, 2, Vector3fD(torch.rand(4, 3, generator=g) * 3.0 + 1.0))
-    metal.specular_reflectance = psdr_cuda.Bitmap3fD(5, 4, Vector3fD(torch.rand(20, 3, generator=g) * 0.5 + 0.5))
-    metal.m_anisotropic = True
-    metal.id = "rough_tex"
-    sc.add_bsdf(metal)
-    floor = [m for m in sc.m_meshes if m.m_has_uv][0]
-    floor.bsdf = metal
-    floor.use_face_normals = False
-    sc.configure()
-    return sc
 
 
 @pytest.mark.parametrize("kw", [dict(bsdf_samples=1, light_samples=1), dict(integrator=_abi.INTEGRATOR_PATH, max_depth=2)])
