@@ -40,7 +40,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(LaunchCtx cx, int m, const flo
 //   * LANE REFILL: a lane whose ray is done writes its hit row and takes the next request at the following leaf boundary -- the wave
 //     keeps a block of 64 requests in registers and hands them out by rank (ds_bpermute), so every node step runs with (nearly) all lanes busy;
 //   * output: hit[dest] = (tri, u, v, t) of the closest TREE hit (tri < 0: none), the same leaf test as every other walk of the library.
-constexpr int kTraceBlock = 1024, kTraceNodeStride = 80, kTraceStackMax = 16;
+// (kTraceBlock, kTraceNodeStride, kTraceStackMax: psdr_host.h, beside the launch plan that shares them, psdr_tree_plan.h plan_wf_trace)
 #ifndef PSDR_TRACE_SERVICE_MIN
 #define PSDR_TRACE_SERVICE_MIN 16
 #endif
@@ -482,9 +482,7 @@ void fill_top(const psdr_scene_s *h, SceneView &sc) {
     std::memcpy(sc.tiny, h->tiny, sizeof(h->tiny));
     std::memcpy(sc.tiny_meta, h->tiny_meta, sizeof(h->tiny_meta));
     sc.n_blas = h->n_blas;
-    std::memcpy(sc.blas_lo, h->blas_lo, sizeof(h->blas_lo));
-    std::memcpy(sc.blas_hi, h->blas_hi, sizeof(h->blas_hi));
-    for (int k = 0; k < h->n_blas; ++k) std::memcpy(&sc.blas_hi[k].w, &h->blas_root4[k], 4);
+    pack_blas_boxes(h, sc.blas_lo, sc.blas_hi);
     sc.nodes4 = h->wide ? h->d_nodes4 : nullptr; sc.root4 = h->root4;
 }
 
@@ -582,6 +580,54 @@ int primary_edge_order(psdr_scene_s *h, const LaunchCtx &cx, long long i0, long 
     return 0;
 }
 
+// ---- steps the tree builds share (the device build below, the host build behind psdr_bvh_build)
+// Growth of a buffer of the handle OUTSIDE a render call (inside one: scratch_reserve) to `need` elements of bytes_each: frees, nulls the pointer, zeroes the
+// capacity, allocates, then records the capacity -- after a failed allocation the handle holds (nullptr, 0), never a freed pointer that psdr_scene_destroy
+// would free a second time.  `with`: a second buffer under the same capacity (with_bytes_each per element) that grows in the same step.
+template <class A, class B = void>
+static int device_grow(A *&ptr, size_t &cap, size_t need, size_t bytes_each, B **with = nullptr, size_t with_bytes_each = 0) {
+    if (need <= cap) return 0;
+    if (ptr) (void) hipFree(ptr);
+    if (with && *with) (void) hipFree(*with);
+    ptr = nullptr; cap = 0;
+    if (with) *with = nullptr;
+    HIP_TRY(hipMalloc(&ptr, need * bytes_each));
+    if (with) HIP_TRY(hipMalloc(with, need * with_bytes_each));
+    cap = need;
+    return 0;
+}
+static int grow_tree(psdr_scene_s *h, size_t nodes, size_t btri_rows) {
+    if (int rc = device_grow(h->d_nodes, h->cap_nodes, std::max<size_t>(nodes, 16), sizeof(BvhNode))) return rc;
+    return device_grow(h->d_btris, h->cap_btris, btri_rows, sizeof(float4));
+}
+// The host copy of emitter_i (hot gradient rows, LDS table sizes, two-level eligibility), refreshed by every build: enqueued on s, there after the caller's
+// next synchronise
+static int fetch_emitters(psdr_scene_s *h, hipStream_t s) {
+    h->emitter_i.assign((size_t) std::max(h->desc.num_emitters, 0) * PSDR_EMITTER_I_STRIDE, 0);
+    if (h->desc.num_emitters > 0 && h->desc.emitter_i)
+        HIP_TRY(hipMemcpyAsync(h->emitter_i.data(), h->desc.emitter_i, h->emitter_i.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+// The device side of the hot rows (hot_row_list): slot -> triangle copied up, triangle -> slot (-1: not cached) scattered from it
+static int upload_hot_rows(psdr_scene_s *h, int T, const std::vector<int32_t> &tris, hipStream_t s) {
+    if (int rc = device_grow(h->d_hot_map, h->hot_cap, (size_t) T, sizeof(int32_t))) return rc;
+    if (!h->d_hot_tris) HIP_TRY(hipMalloc(&h->d_hot_tris, kMaxHotRows * sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(h->d_hot_map, 0xff, (size_t) T * sizeof(int32_t), s));
+    HIP_TRY(hipMemcpyAsync(h->d_hot_tris, tris.data(), tris.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_scatter_hot, dim3(1), dim3(256), 0, s, h->d_hot_map, h->d_hot_tris, (int) tris.size());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));            // `tris` is the caller's
+    h->hot_rows = (int) tris.size();
+    return 0;
+}
+// nothing travels in the kernel arguments until the build says so
+static void reset_top(psdr_scene_s *h) { h->n_tiny = 0; h->aa_cnt = 0; h->n_blas = 0; h->n_inline = 0; h->have_occ = false; h->emit_rows = 0; }
+// what the refit path needs of a finished build (the levels are the caller's): the triangle count, the padding, the reference area
+static void finish_build(psdr_scene_s *h, int T, float pad, float area, bool lbvh, bool refit_ok) {
+    h->tree_tris = T; h->refits_since_build = 0; h->num_builds++; h->bvh_pad = pad; h->built_area = area;
+    h->refit_ok = refit_ok; h->lbvh = lbvh; h->have_bvh = true;
+}
+
 // ---- device tree (psdr_lbvh.h).  Layout of the scratch block: what the refit needs first, the build temporaries behind.
 struct LbvhScratch {
     LbvhInfo *info; uint32_t *bounds; int32_t *node_parent, *leaf_parent; uint32_t *arrivals;
@@ -628,24 +674,9 @@ int lbvh_build(psdr_scene_s *h, hipStream_t s, bool &fallback) {
     HIP_TRY(rocprim::radix_sort_pairs_desc(nullptr, t2, nk, nk, nv, nv, (size_t) T, 0, 32, s));
     const size_t sort_tmp = std::max(t1, t2);
     const size_t need = lbvh_layout(nullptr, T, sort_tmp).total;
-    if (need > h->lbvh_bytes) {
-        if (h->d_lbvh) (void) hipFree(h->d_lbvh);
-        h->d_lbvh = nullptr; h->lbvh_bytes = 0;
-        HIP_TRY(hipMalloc(&h->d_lbvh, need));
-        h->lbvh_bytes = need;
-    }
+    if (int rc = device_grow(h->d_lbvh, h->lbvh_bytes, need, 1)) return rc;
     const LbvhScratch L = lbvh_layout(h->d_lbvh, T, sort_tmp);
-    if ((size_t) (T - 1) > h->cap_nodes) {
-        if (h->d_nodes) (void) hipFree(h->d_nodes);
-        h->cap_nodes = std::max<size_t>((size_t) T, 16);
-        HIP_TRY(hipMalloc(&h->d_nodes, h->cap_nodes * sizeof(BvhNode)));
-    }
-    if ((size_t) T * 3 > h->cap_btris) {
-        if (h->d_btris) (void) hipFree(h->d_btris);
-        h->cap_btris = (size_t) T * 3;
-        HIP_TRY(hipMalloc(&h->d_btris, h->cap_btris * sizeof(float4)));
-    }
-    if (!h->d_refit_area) HIP_TRY(hipMalloc(&h->d_refit_area, sizeof(float)));
+    if (int rc = grow_tree(h, (size_t) T, (size_t) T * 3)) return rc;
     const dim3 gT((T + kBlock - 1) / kBlock), blk(kBlock);
     HIP_TRY(hipMemsetAsync(L.info, 0, sizeof(LbvhInfo), s));
     HIP_TRY(hipMemsetAsync(L.bounds, 0xff, 3 * 4, s));
@@ -666,8 +697,7 @@ int lbvh_build(psdr_scene_s *h, hipStream_t s, bool &fallback) {
     if (info.bad) return fail("psdr_bvh_build: non-finite vertex");
     if (int rc = lbvh_fit(h, L, info.pad, s)) return rc;
     hipLaunchKernelGGL(k_lbvh_depth, gT, blk, 0, s, T, L.node_parent, L.leaf_parent, L.info);
-    // hot rows of the gradient cache: emitter triangles, then the largest triangles (area keys sorted on the device)
-    constexpr int kMaxHotRows = 200;
+    // hot rows of the gradient cache (hot_row_list): emitter triangles, then the largest triangles (area keys sorted on the device)
     hipLaunchKernelGGL(k_lbvh_area_keys, gT, blk, 0, s, h->desc.tri_info, T, L.keys, L.vals);
     HIP_TRY(hipGetLastError());
     tmp_bytes = L.sort_tmp_bytes;
@@ -678,38 +708,13 @@ int lbvh_build(psdr_scene_s *h, hipStream_t s, bool &fallback) {
     HIP_TRY(hipMemcpyAsync(&info, L.info, sizeof(info), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&area, h->d_refit_area, sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(by_area.data(), L.vals2, (size_t) top * 4, hipMemcpyDeviceToHost, s));
-    h->emitter_i.assign((size_t) std::max(h->desc.num_emitters, 0) * PSDR_EMITTER_I_STRIDE, 0);
-    if (h->desc.num_emitters > 0 && h->desc.emitter_i)
-        HIP_TRY(hipMemcpyAsync(h->emitter_i.data(), h->desc.emitter_i, h->emitter_i.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (int rc = fetch_emitters(h, s)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     if (info.depth > kBvhStack - 2) { fallback = true; return 0; }
-    std::vector<int32_t> tris;
-    {
-        auto add = [&](int t) {
-            if (t < 0 || t >= T || (int) tris.size() >= kMaxHotRows) return;
-            if (std::find(tris.begin(), tris.end(), t) == tris.end()) tris.push_back(t);
-        };
-        for (int e = 0; e < h->desc.num_emitters; ++e) {
-            const int32_t *ei = h->emitter_i.data() + (size_t) e * PSDR_EMITTER_I_STRIDE;
-            for (int f = 0; f < ei[2] && f < 64; ++f) add(ei[1] + f);
-        }
-        for (int i = 0; i < top; ++i) add(by_area[(size_t) i]);
-    }
-    if ((size_t) T > h->hot_cap) {
-        if (h->d_hot_map) (void) hipFree(h->d_hot_map);
-        if (h->d_hot_tris) (void) hipFree(h->d_hot_tris);
-        h->hot_cap = (size_t) T;
-        HIP_TRY(hipMalloc(&h->d_hot_map, h->hot_cap * sizeof(int32_t)));
-        HIP_TRY(hipMalloc(&h->d_hot_tris, kMaxHotRows * sizeof(int32_t)));
-    }
-    HIP_TRY(hipMemsetAsync(h->d_hot_map, 0xff, (size_t) T * sizeof(int32_t), s));
-    HIP_TRY(hipMemcpyAsync(h->d_hot_tris, tris.data(), tris.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_scatter_hot, dim3(1), dim3(256), 0, s, h->d_hot_map, h->d_hot_tris, (int) tris.size());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));            // `tris` dies at return
-    h->hot_rows = (int) tris.size(); h->hot_identity = false;
+    if (int rc = upload_hot_rows(h, T, hot_row_list(T, false, h->emitter_i, h->desc.num_emitters, by_area.data(), top), s)) return rc;
+    h->hot_identity = false;
     h->root = 0; h->bvh_depth = info.depth; h->num_nodes = T - 1; h->num_btris = T;
-    h->n_tiny = 0; h->aa_cnt = 0; h->n_blas = 0; h->n_inline = 0; h->have_occ = false; h->emit_rows = 0;
+    reset_top(h);
     if (use_wide_tree(h, false)) {
         // the 4-wide tree over the device-built BVH2: its topology is decided on the host (one read-back of the node array; the collapse is
         // O(T)): 263 k triangles +~15 ms on top of the 2 ms device build -- only where a launch would walk it
@@ -718,9 +723,8 @@ int lbvh_build(psdr_scene_s *h, hipStream_t s, bool &fallback) {
         HIP_TRY(hipStreamSynchronize(s));
         if (int rc = bvh4_build(h, host_nodes, std::vector<int32_t>{0}, false, s)) return rc;
     } else { h->wide = false; h->num_nodes4 = 0; h->stack_need4 = 0; }
-    h->tree_tris = T; h->refits_since_build = 0; h->num_builds++; h->bvh_pad = info.pad; h->built_area = area;
     h->level_start.clear();
-    h->refit_ok = true; h->lbvh = true; h->have_bvh = true;
+    finish_build(h, T, info.pad, area, true, true);
     return 0;
 }
 
@@ -743,14 +747,7 @@ int bvh4_build(psdr_scene_s *h, const std::vector<BvhNode> &nodes, const std::ve
     h->root4 = roots2.size() == 1 ? tp.roots[0] : 0;
     for (size_t k = 0; k < roots2.size() && k < (size_t) kMaxBlas; ++k) h->blas_root4[k] = tp.roots[k];
     if (tp.n4 == 0) return 0;
-    if ((size_t) tp.n4 > h->cap_nodes4) {
-        if (h->d_nodes4) (void) hipFree(h->d_nodes4);
-        if (h->d_topo4) (void) hipFree(h->d_topo4);
-        h->d_nodes4 = nullptr; h->d_topo4 = nullptr;
-        h->cap_nodes4 = (size_t) tp.n4;
-        HIP_TRY(hipMalloc(&h->d_nodes4, h->cap_nodes4 * sizeof(Bvh4Node)));
-        HIP_TRY(hipMalloc(&h->d_topo4, h->cap_nodes4 * 8 * sizeof(int32_t)));
-    }
+    if (int rc = device_grow(h->d_nodes4, h->cap_nodes4, (size_t) tp.n4, sizeof(Bvh4Node), &h->d_topo4, 8 * sizeof(int32_t))) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_topo4, tp.child.data(), (size_t) tp.n4 * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->d_topo4 + (size_t) tp.n4 * 4, tp.src.data(), (size_t) tp.n4 * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (int rc = bvh4_refill(h, s)) return rc;
@@ -763,34 +760,16 @@ int launch_wf_trace(psdr_scene_s *h, const float4 *req, const int32_t *count, lo
     TraceArgs a{};
     a.sec_edge_faces = h->desc.sec_edge_faces;
     if (ign && !a.sec_edge_faces) ign = false;
-    std::memcpy(a.blas_lo, h->blas_lo, sizeof(a.blas_lo));
-    std::memcpy(a.blas_hi, h->blas_hi, sizeof(a.blas_hi));
-    for (int k = 0; k < h->n_blas; ++k) std::memcpy(&a.blas_hi[k].w, &h->blas_root4[k], 4);
+    pack_blas_boxes(h, a.blas_lo, a.blas_hi);
     a.nodes4 = h->d_nodes4; a.btris = h->d_btris; a.req = req; a.count = count; a.hit = hit; a.sub_cap = sub_cap; a.n_blas = h->n_blas;
-    // LDS: stacks first in the budget (S + 1 columns: the unconditional stores of a node step may touch the entry above the top), the tree in the rest.
-    // TWO workgroups per CU (8 waves per SIMD, <= 64 VGPRs), each with half of the LDS -- stack columns of 8 entries (deeper ones, rare, in the
-    // overflow columns), fewer staged nodes -- where the walk gains more from the second set of waves than it loses to the smaller staging:
-    // a forest that does not fit the LDS anyway (C5: trace stage 326 -> 307 us) or a large launch (C4 shard: 754 -> 690 us); the 4 M-slot launch on
-    // the bunny, whose whole tree fits one workgroup's LDS, is 2.5 % faster with one (profiles/r04_trace_wg2_abk.txt).  Option trace_wg2: -1 this
-    // rule, 0 never, n > 0 always with columns of n entries.
-    const int full_S = std::min(h->stack_need4, kTraceStackMax);
-    const bool tree_fits = (long long) h->num_nodes4 * kTraceNodeStride + (long long) (full_S + 1) * kTraceBlock * 4 + 1024 <= (long long) h->lds_limit;
-    const bool wg2 = h->lds_limit >= 160 * 1024 && (h->opt.trace_wg2 > 0 || (h->opt.trace_wg2 < 0 && (!tree_fits || sub_cap * kWfSub >= (1ll << 25))));
-    const int S = std::min(h->stack_need4, wg2 ? std::min(h->opt.trace_wg2 > 0 ? h->opt.trace_wg2 : 8, kTraceStackMax) : kTraceStackMax);
-    const bool ovf = h->stack_need4 > S;
-    const int stack_bytes = (S + 1) * kTraceBlock * 4;
-    const int room = (wg2 ? h->lds_limit / 2 : h->lds_limit) - 1024 - stack_bytes;                 // 1 KB: the kernel's static LDS
-    a.n_lnodes = std::max(0, std::min(h->num_nodes4, room / kTraceNodeStride));
-    a.off_stack = a.n_lnodes * kTraceNodeStride;
-    a.stack_entries = S;
-    const int grid = wg2 ? 2 * h->num_cus : h->num_cus;
-    if (ovf) {
-        a.ovf_stride = grid * kTraceBlock;
-        const size_t need = (size_t) a.ovf_stride * (size_t) (h->stack_need4 - S) * sizeof(int32_t);
-        if (int rc = scratch_reserve(reinterpret_cast<void **>(&h->d_trace_ovf), &h->trace_ovf_bytes, need, s, "trace kernel's overflow stack columns")) return rc;
+    const TracePlan p = plan_wf_trace(h, sub_cap);
+    a.n_lnodes = p.n_lnodes; a.off_stack = p.off_stack; a.stack_entries = p.stack_entries; a.ovf_stride = p.ovf_stride;
+    if (p.ovf) {
+        if (int rc = scratch_reserve(reinterpret_cast<void **>(&h->d_trace_ovf), &h->trace_ovf_bytes, p.ovf_bytes, s, "trace kernel's overflow stack columns")) return rc;
         a.ovf = h->d_trace_ovf;
     }
-    const int dyn = a.off_stack + stack_bytes;
+    const bool wg2 = p.wg2, ovf = p.ovf;
+    const int grid = p.grid, dyn = p.dyn;
 #define PSDR_LAUNCH_TRACE_I(MULTI, OVF, IGN, WPE)                                                                                                           \
     do { static bool attr_set = false;                                                                                                                      \
          if (!attr_set) { if (int rc = allow_dynamic_lds(&k_wf_trace<MULTI, OVF, IGN, WPE>, 160 * 1024 - 1024)) return rc; attr_set = true; }                     \
@@ -806,19 +785,15 @@ int launch_wf_trace(psdr_scene_s *h, const float4 *req, const int32_t *count, lo
 
 // hit rows [slots * rays_per_slot], one mask word per slot, the request queue (64 sub-queues, every ray can be a request) and its counters (zeroed here)
 int probe_buffers(psdr_scene_s *h, long long slots, int rays_per_slot, ProbeBuffers &pb, hipStream_t s, int per_cu) {
-    const long long rays = slots * rays_per_slot;
-    const long long blocks = ((long long) launch_blocks(h, slots, per_cu) + kWfSub - 1) / kWfSub * kWfSub;
-    const long long trips = (slots + blocks * kBlock - 1) / (blocks * kBlock);
-    pb.sub_cap = (blocks / kWfSub) * trips * kBlock * rays_per_slot;          // block b appends to queue b % kWfSub
-    const size_t cnt_bytes = (size_t) kWfSub * kWfCountStride * sizeof(int32_t);
-    const size_t need = cnt_bytes + (size_t) rays * sizeof(float4) + (((size_t) slots * 4 + 255) & ~(size_t) 255) + (size_t) 2 * pb.sub_cap * kWfSub * sizeof(float4);
-    if (int rc = scratch_reserve(&h->d_probe, &h->probe_bytes, need, s, "probe buffers (hit rows, masks, trace requests)")) return rc;
+    const ProbePlan pl = plan_probe_buffers(h, slots, rays_per_slot, per_cu);
+    pb.sub_cap = pl.sub_cap;
+    if (int rc = scratch_reserve(&h->d_probe, &h->probe_bytes, pl.total, s, "probe buffers (hit rows, masks, trace requests)")) return rc;
     char *p = reinterpret_cast<char *>(h->d_probe);
-    pb.count = reinterpret_cast<int32_t *>(p); p += cnt_bytes;
-    pb.hit = reinterpret_cast<float4 *>(p); p += (size_t) rays * sizeof(float4);
-    pb.mask = reinterpret_cast<uint32_t *>(p); p += ((size_t) slots * 4 + 255) & ~(size_t) 255;
+    pb.count = reinterpret_cast<int32_t *>(p); p += pl.cnt_bytes;
+    pb.hit = reinterpret_cast<float4 *>(p); p += pl.hit_bytes;
+    pb.mask = reinterpret_cast<uint32_t *>(p); p += pl.mask_bytes;
     pb.req = reinterpret_cast<float4 *>(p);
-    HIP_TRY(hipMemsetAsync(pb.count, 0, cnt_bytes, s));
+    HIP_TRY(hipMemsetAsync(pb.count, 0, pl.cnt_bytes, s));
     return 0;
 }
 
@@ -993,15 +968,204 @@ static hipError_t copy_on_stream(void *dst, const void *src, size_t bytes, hipMe
 }
 // SceneView::emit_rows from the handle's current primitive table and its host copy of the emitter table
 static void update_emit_rows(psdr_scene_s *h) {
-    std::vector<char> is_em((size_t) std::max(h->desc.num_tris, 0), 0);
-    for (int e = 0; e < h->desc.num_emitters && (size_t) (e + 1) * PSDR_EMITTER_I_STRIDE <= h->emitter_i.size(); ++e) {
-        const int32_t *ei = h->emitter_i.data() + (size_t) e * PSDR_EMITTER_I_STRIDE;
-        if (e == h->desc.env_emitter) { h->emit_rows = 0; return; }
-        for (int f = 0; f < ei[2]; ++f) if (ei[1] + f >= 0 && ei[1] + f < h->desc.num_tris) is_em[(size_t) (ei[1] + f)] = 1;
-    }
-    h->emit_rows = h->n_tiny > 0 ? tiny_emitter_rows(h->tiny_meta, h->n_tiny, h->aa_cnt, is_em) : 0u;
+    h->emit_rows = 0;
+    if (h->n_tiny > 0 && emit_rows_wanted(h))
+        h->emit_rows = tiny_emitter_rows(h->tiny_meta, h->n_tiny, h->aa_cnt, emitter_triangle_mask(h->emitter_i, h->desc.num_emitters, h->desc.num_tris));
 }
-static int bvh_build_or_refit(psdr_scene_s *h, hipStream_t s);
+
+// ---- refit (the decisions: psdr_tree_plan.h refit_candidate, refit_choice, refit_inline_fits)
+static void refit_done(psdr_scene_s *h) { h->refits_since_build++; h->num_refits++; h->have_bvh = true; }
+// Is the emitter layout still the one of the handle's host copy?  One small device-to-host copy per refit candidate; a changed layout takes the full build.
+static int emitters_unchanged(psdr_scene_s *h, hipStream_t s, bool &same) {
+    same = (size_t) std::max(h->desc.num_emitters, 0) * PSDR_EMITTER_I_STRIDE == h->emitter_i.size();
+    if (!same || h->emitter_i.empty()) return 0;
+    same = h->desc.emitter_i != nullptr;
+    if (!same) return 0;
+    std::vector<int32_t> now(h->emitter_i.size());
+    HIP_TRY(copy_on_stream(now.data(), h->desc.emitter_i, now.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    same = std::memcmp(now.data(), h->emitter_i.data(), now.size() * sizeof(int32_t)) == 0;
+    return 0;
+}
+// Refit of a host-built tree: the leaf triangles again, the boxes level by level from the bottom, then what travels in the kernel arguments.
+// fits = false: the refitted inline primitives are too many for the kernel arguments -- the caller builds anew.
+static int host_tree_refit(psdr_scene_s *h, hipStream_t s, bool &fits) {
+    fits = true;
+    HIP_TRY(hipMemsetAsync(h->d_refit_area, 0, sizeof(float), s));
+    hipLaunchKernelGGL(k_refit_leaves, dim3((h->num_btris + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h->d_btris, h->desc.tri_info, h->num_btris);
+    for (int l = (int) h->level_start.size() - 2; l >= 0; --l) {
+        const int first = h->level_start[l], count = h->level_start[l + 1] - first;
+        hipLaunchKernelGGL(k_refit_level, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h->d_nodes, h->d_btris, first, count, h->bvh_pad, h->d_refit_area);
+    }
+    HIP_TRY(hipGetLastError());
+    if (int rc = bvh4_refill(h, s)) return rc;          // the 4-wide nodes from the refitted boxes
+    if (h->n_blas == 0) return 0;
+    // two-level tree: the kernel arguments carry the inline primitives and the tree boxes -- fetch the refitted ones
+    float4 top[kMaxInlineTris * 3 + 2 * kMaxBlas];
+    hipLaunchKernelGGL(k_gather_top, dim3(1), dim3(64), 0, s, h->d_top, h->d_nodes, h->desc.tri_info, h->d_inline_ids, h->n_inline, h->n_blas);
+    HIP_TRY(hipMemcpyAsync(top, h->d_top, sizeof(top), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<float4> tris(top, top + 3 * (size_t) h->n_inline), prims;
+    pack_tiny_prims(tris, prims);
+    fits = refit_inline_fits((int) prims.size() / 3);
+    if (!fits) return 0;
+    h->n_tiny = tiny_plane_form(prims, h->tiny, h->tiny_meta, &h->aa_cnt, h->aa_enabled);
+    update_emit_rows(h);
+    for (int k = 0; k < h->n_blas; ++k) {
+        const float w = h->blas_lo[k].w;
+        h->blas_lo[k] = top[kMaxInlineTris * 3 + k]; h->blas_lo[k].w = w;
+        h->blas_hi[k] = top[kMaxInlineTris * 3 + kMaxBlas + k];
+    }
+    return 0;
+}
+// done = false (and 0 returned): no refit, or one that did not fit -- a full build follows
+static int try_refit(psdr_scene_s *h, int T, bool tiny, hipStream_t s, bool &done) {
+    done = false;
+    if (!refit_candidate(h, T, tiny)) return 0;
+    bool emitters_same = false;
+    if (int rc = emitters_unchanged(h, s, emitters_same)) return rc;
+    const bool stands = forest_stands(h);
+    if (refit_choice(h, emitters_same, stands, h->built_area) == kRefitNone) return 0;          // whatever the area: spare the read-back
+    float prev_area = h->built_area;
+    if (h->refits_since_build > 0) {        // of the PREVIOUS refit (done long ago), read on the stream that wrote it
+        HIP_TRY(hipMemcpyAsync(&prev_area, h->d_refit_area, sizeof(float), hipMemcpyDeviceToHost, h->refit_stream));
+        HIP_TRY(hipStreamSynchronize(h->refit_stream));
+    }
+    const RefitKind kind = refit_choice(h, emitters_same, stands, prev_area);
+    if (kind == kRefitNone) return 0;
+    h->refit_stream = s;
+    if (kind == kRefitDeviceTree) {
+        if (int rc = lbvh_refit(h, s)) return rc;
+        if (int rc = bvh4_refill(h, s)) return rc;
+        done = true;
+    } else if (int rc = host_tree_refit(h, s, done)) return rc;
+    if (done) refit_done(h);
+    return 0;
+}
+
+// ---- host build: binned SAH over a host copy of the table (psdr_bvh_build.h), as a two-level tree (ForestBuilder) or as one tree (Builder)
+struct HostTree {
+    Builder b; ForestBuilder fb;
+    bool forest = false;
+    int32_t root = 0;
+    std::vector<float4> top_prims;          // two-level tree: the inline triangles, paired (pack_tiny_prims)
+    std::vector<BvhNode> &nodes() { return forest ? fb.nodes : b.nodes; }
+    std::vector<float4> &btris() { return forest ? fb.btris : b.btris; }
+};
+// which tree (forest_candidate, ForestBuilder::eligible, forest_kept), and the build itself
+static int host_tree_construct(psdr_scene_s *h, int T, const std::vector<float> &rows, hipStream_t s, HostTree &t) {
+    std::vector<int32_t> tri_mesh;
+    if (forest_candidate(h, T)) {
+        tri_mesh.resize((size_t) T);
+        HIP_TRY(copy_on_stream(tri_mesh.data(), h->desc.tri_mesh, tri_mesh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        t.forest = ForestBuilder::eligible(tri_mesh.data(), T, h->desc.num_meshes) && (!PSDR_FOREST_LDS_TABLES || small_tables_fit(h));
+    }
+    t.b.kMaxLeaf = t.fb.max_leaf = h->opt.bvh_maxleaf; t.b.kTraversalCost = t.fb.traversal_cost = h->opt.bvh_tcost;
+    if (t.forest) {
+        if (const char *err = t.fb.run(rows.data(), tri_mesh.data(), T, h->desc.num_meshes)) return fail(err);
+        pack_tiny_prims(t.fb.inline_tris, t.top_prims);
+        // (two bunnies and a light quad: PathTracer(3) 2.9 ms on one tree against 3.1 on the forest -- the two-level tree is for walls around objects)
+        if (!forest_kept(h, (int) t.top_prims.size() / 3, (int) t.fb.inline_tris.size() / 3)) { t.forest = false; t.fb = ForestBuilder(); }
+    }
+    if (!t.forest) { if (const char *err = t.b.run(rows.data(), T, t.root)) return fail(err); }
+    return 0;
+}
+// the tree, the hot rows of the gradient cache (by_area: largest triangles first) and the 4-wide tree onto the device
+static int host_tree_upload(psdr_scene_s *h, int T, bool tiny, const std::vector<float> &rows, HostTree &t, hipStream_t s) {
+    std::vector<BvhNode> &nodes = t.nodes();
+    std::vector<float4> &btris = t.btris();
+    if (int rc = grow_tree(h, nodes.size(), btris.size())) return rc;
+    if (!nodes.empty()) HIP_TRY(hipMemcpyAsync(h->d_nodes, nodes.data(), nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_btris, btris.data(), btris.size() * sizeof(float4), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));     // host vectors die at return
+    std::vector<int32_t> by_area((size_t) T);
+    for (int i = 0; i < T; ++i) by_area[(size_t) i] = i;
+    const int top = std::min(T, kMaxHotRows);
+    std::partial_sort(by_area.begin(), by_area.begin() + top, by_area.end(),
+                      [&](int a, int c) { return rows[(size_t) a * PSDR_TRI_STRIDE + 21] > rows[(size_t) c * PSDR_TRI_STRIDE + 21]; });
+    if (int rc = upload_hot_rows(h, T, hot_row_list(T, tiny, h->emitter_i, h->desc.num_emitters, by_area.data(), top), s)) return rc;
+    h->hot_identity = tiny;
+    h->root = t.root;
+    h->bvh_depth = t.forest ? t.fb.max_depth : t.b.max_depth; h->num_nodes = (int) nodes.size(); h->num_btris = (int) btris.size() / 3;
+    return bvh4_build(h, nodes, t.forest ? t.fb.roots : std::vector<int32_t>{t.root}, t.forest, s);
+}
+// tail of a two-level tree: the inline primitives and the boxes + roots of the per-mesh trees travel in the kernel arguments
+static int forest_tail(psdr_scene_s *h, HostTree &t, hipStream_t s) {
+    ForestBuilder &fb = t.fb;
+    h->n_tiny = tiny_plane_form(t.top_prims, h->tiny, h->tiny_meta, &h->aa_cnt, h->aa_enabled);
+    update_emit_rows(h);
+    h->n_inline = (int) fb.inline_ids.size();
+    h->n_blas = (int) fb.roots.size();
+    for (int k = 0; k < h->n_blas; ++k) {
+        float lo[3], hi[3];
+        fb.tree_box(k, lo, hi);
+        h->blas_lo[k] = float4{lo[0], lo[1], lo[2], 0.f}; h->blas_hi[k] = float4{hi[0], hi[1], hi[2], 0.f};
+        std::memcpy(&h->blas_lo[k].w, &fb.roots[(size_t) k], 4);
+    }
+    if (!h->d_top) HIP_TRY(hipMalloc(&h->d_top, sizeof(float4) * (kMaxInlineTris * 3 + 2 * kMaxBlas)));
+    if (!h->d_inline_ids) HIP_TRY(hipMalloc(&h->d_inline_ids, sizeof(int32_t) * kMaxInlineTris));
+    if (h->n_inline) HIP_TRY(copy_on_stream(h->d_inline_ids, fb.inline_ids.data(), sizeof(int32_t) * (size_t) h->n_inline, hipMemcpyHostToDevice, s));
+    return 0;
+}
+// tail of a scene without a tree: every triangle travels in the kernel arguments, with the occluder rows of the light rays
+static int tiny_tail(psdr_scene_s *h, int T, HostTree &t, hipStream_t s) {
+    std::vector<float4> prims;
+    std::vector<int> row_of_prim;
+    pack_tiny_prims(t.b.btris, prims);           // walls as parallelograms: half the tests
+    h->n_tiny = tiny_plane_form(prims, h->tiny, h->tiny_meta, &h->aa_cnt, h->aa_enabled, &row_of_prim);
+    update_emit_rows(h);
+    // occluder rows of the light rays (SceneView::occ): which primitives can lie between a triangle and an emitter triangle
+    if (!(T <= 32 && h->n_tiny <= 32)) return 0;
+    const std::vector<char> is_em = emitter_triangle_mask(h->emitter_i, h->desc.num_emitters, T);
+    std::vector<uint32_t> occ;
+    if (h->opt.occ_rows != 0) tiny_occluder_rows(prims, row_of_prim, T, is_em, occ);
+    else occ.assign((size_t) T * T, 0xffffffffu);
+    if (int rc = device_grow(h->d_occ, h->occ_cap, std::max<size_t>(occ.size(), 32 * 32), sizeof(uint32_t))) return rc;
+    HIP_TRY(copy_on_stream(h->d_occ, occ.data(), occ.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    h->have_occ = true;
+    h->occ_max_rows = occluder_max_rows(occ, is_em, T, h->n_tiny);
+    return 0;
+}
+static int host_build(psdr_scene_s *h, int T, bool tiny, hipStream_t s) {
+    std::vector<float> rows((size_t) T * PSDR_TRI_STRIDE);
+    HIP_TRY(hipMemcpyAsync(rows.data(), h->desc.tri_info, rows.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = fetch_emitters(h, s)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    HostTree t;
+    if (int rc = host_tree_construct(h, T, rows, s, t)) return rc;
+    if (int rc = host_tree_upload(h, T, tiny, rows, t, s)) return rc;
+    reset_top(h);
+    if (t.forest) { if (int rc = forest_tail(h, t, s)) return rc; }
+    else if (tiny) { if (int rc = tiny_tail(h, T, t, s)) return rc; }
+    // what the refit path needs: the levels of the breadth-first node order, the padding, the reference area
+    double area = 0.0;
+    bool refit_ok = true;
+    if (t.forest) {
+        h->level_start = t.fb.level_start;
+        for (const BvhNode &n : t.fb.nodes) area += node_area(n);
+        for (int32_t r : t.fb.roots) if (r < 0) refit_ok = false;     // k_gather_top reads the roots as nodes 0 .. n_blas-1
+    } else area = tree_levels_and_area(t.b.nodes, t.root, h->level_start);
+    finish_build(h, T, t.forest ? t.fb.pad : t.b.pad, (float) area, false, refit_ok);
+    return 0;
+}
+
+// psdr_bvh_build: refit the tree on the device where that is allowed, else build it on the device where that is wanted, else on the host
+static int bvh_build_or_refit(psdr_scene_s *h, hipStream_t s) {
+    const int T = h->desc.num_tris;
+    const bool tiny = tiny_scene(h, T);
+    h->kept.valid = false;                  // records of a value sweep belong to the tree they were traced with
+    bool done = false;
+    if (int rc = try_refit(h, T, tiny, s, done)) return rc;
+    if (done) return 0;
+    h->lbvh = false;
+    if (!h->d_refit_area) HIP_TRY(hipMalloc(&h->d_refit_area, sizeof(float)));
+    if (device_build_wanted(h, T, tiny)) {
+        bool fallback = false;          // too few triangles, or a tree deeper than the traversal stack: the host builder has to do it
+        if (int rc = lbvh_build(h, s, fallback)) return rc;
+        if (!fallback) return 0;
+    }
+    return host_build(h, T, tiny, s);
+}
 // A build that returns an error has usually written part of the new tree over the old one already (lbvh_build: the leaf records and the children,
 // before it learns of a non-finite vertex; the host paths: whatever was copied up before a later step failed) while the host-side fields still
 // describe the previous tree: the handle is left WITHOUT a tree -- the next launch is refused, the next build is a full one.
@@ -1010,233 +1174,6 @@ int psdr_bvh_build(psdr_scene_t h, void *stream) {
     const int rc = bvh_build_or_refit(h, (hipStream_t) stream);
     if (rc) { h->have_bvh = false; h->refit_ok = false; }
     return rc;
-}
-static int bvh_build_or_refit(psdr_scene_s *h, hipStream_t s) {
-    const int T = h->desc.num_tris;
-    h->kept.valid = false;                  // records of a value sweep belong to the tree they were traced with
-    // ---- refit: same triangle count as the tree on the device and the tree has not degraded
-    const bool tiny = h->tiny_enabled && T <= kTinyTris;        // the triangles travel in the kernel arguments: host copy needed
-    // The host copy of emitter_i (LDS table sizes, two-level eligibility, hot gradient rows) is refreshed by the build paths below only: a
-    // refit must not run on when the emitter layout changed under an unchanged triangle count -- the kernels would stage too few entries of
-    // face_cmf / face_pmf.  One small device-to-host copy per refit candidate; a changed layout takes the full build.
-    bool emitters_same = (size_t) std::max(h->desc.num_emitters, 0) * PSDR_EMITTER_I_STRIDE == h->emitter_i.size();
-    if (emitters_same && !h->emitter_i.empty() && h->refit_enabled && !tiny && h->refit_ok && h->tree_tris == T && h->num_nodes > 0) {
-        std::vector<int32_t> now(h->emitter_i.size());
-        emitters_same = h->desc.emitter_i != nullptr;
-        if (emitters_same) {
-            HIP_TRY(copy_on_stream(now.data(), h->desc.emitter_i, now.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            emitters_same = std::memcmp(now.data(), h->emitter_i.data(), now.size() * sizeof(int32_t)) == 0;
-        }
-    }
-    const bool forest_stands = !(forest_tables(h) && !small_tables_fit(h));      // a two-level tree whose kernels could no longer stage the tables: rebuild as one tree
-    if (h->refit_enabled && !tiny && h->refit_ok && emitters_same && forest_stands && h->tree_tris == T && h->num_nodes > 0 && h->refits_since_build < kMaxRefits) {
-        float prev_area = h->built_area;
-        if (h->refits_since_build > 0) {        // of the PREVIOUS refit (done long ago), read on the stream that wrote it
-            HIP_TRY(hipMemcpyAsync(&prev_area, h->d_refit_area, sizeof(float), hipMemcpyDeviceToHost, h->refit_stream));
-            HIP_TRY(hipStreamSynchronize(h->refit_stream));
-        }
-        if (prev_area <= kRefitAreaGrowth * h->built_area && h->lbvh) {
-            h->refit_stream = s;
-            if (int rc = lbvh_refit(h, s)) return rc;
-            if (int rc = bvh4_refill(h, s)) return rc;
-            h->refits_since_build++;
-            h->num_refits++;
-            h->have_bvh = true;
-            return 0;
-        }
-        if (prev_area <= kRefitAreaGrowth * h->built_area) {
-            bool refit_fits = true;
-            h->refit_stream = s;
-            HIP_TRY(hipMemsetAsync(h->d_refit_area, 0, sizeof(float), s));
-            hipLaunchKernelGGL(k_refit_leaves, dim3((h->num_btris + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h->d_btris, h->desc.tri_info, h->num_btris);
-            for (int l = (int) h->level_start.size() - 2; l >= 0; --l) {
-                const int first = h->level_start[l], count = h->level_start[l + 1] - first;
-                hipLaunchKernelGGL(k_refit_level, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h->d_nodes, h->d_btris, first, count, h->bvh_pad,
-                                   h->d_refit_area);
-            }
-            HIP_TRY(hipGetLastError());
-            if (int rc = bvh4_refill(h, s)) return rc;          // the 4-wide nodes from the refitted boxes
-            if (h->n_blas > 0) {          // the kernel arguments carry the inline primitives and the tree boxes: fetch the refitted ones
-                float4 top[kMaxInlineTris * 3 + 2 * kMaxBlas];
-                hipLaunchKernelGGL(k_gather_top, dim3(1), dim3(64), 0, s, h->d_top, h->d_nodes, h->desc.tri_info, h->d_inline_ids, h->n_inline, h->n_blas);
-                HIP_TRY(hipMemcpyAsync(top, h->d_top, sizeof(top), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                std::vector<float4> tris(top, top + 3 * (size_t) h->n_inline), prims;
-                pack_tiny_prims(tris, prims);
-                // moved wall vertices may no longer pair into parallelograms: more than kTinyTris primitives -> full rebuild below
-                // (which then picks a single tree)
-                refit_fits = (int) prims.size() / 3 <= kTinyTris;
-                if (refit_fits) {
-                    h->n_tiny = tiny_plane_form(prims, h->tiny, h->tiny_meta, &h->aa_cnt, h->aa_enabled);
-                    update_emit_rows(h);
-                    for (int k = 0; k < h->n_blas; ++k) {
-                        const float w = h->blas_lo[k].w;
-                        h->blas_lo[k] = top[kMaxInlineTris * 3 + k]; h->blas_lo[k].w = w;
-                        h->blas_hi[k] = top[kMaxInlineTris * 3 + kMaxBlas + k];
-                    }
-                }
-            }
-            if (refit_fits) {
-                h->refits_since_build++;
-                h->num_refits++;
-                h->have_bvh = true;
-                return 0;
-            }
-        }
-    }
-    // ---- build on the device: large tables (the host build is a D2H of the table + a single-threaded SAH build), or on request
-    h->lbvh = false;
-    if (!tiny && (h->bvh_device_mode == 1 || (h->bvh_device_mode < 0 && T >= kLbvhAutoTris))) {
-        bool fallback = false;
-        if (int rc = lbvh_build(h, s, fallback)) return rc;
-        if (!fallback) return 0;
-    }
-    std::vector<float> rows((size_t) T * PSDR_TRI_STRIDE);
-    HIP_TRY(hipMemcpyAsync(rows.data(), h->desc.tri_info, rows.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    h->emitter_i.assign((size_t) std::max(h->desc.num_emitters, 0) * PSDR_EMITTER_I_STRIDE, 0);
-    if (h->desc.num_emitters > 0 && h->desc.emitter_i)
-        HIP_TRY(copy_on_stream(h->emitter_i.data(), h->desc.emitter_i, h->emitter_i.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    // ---- which tree: two-level (a few small meshes + a few large ones) or one tree over everything
-    std::vector<int32_t> tri_mesh;
-    bool forest = false;
-    if (h->two_level_enabled && h->tiny_enabled && T > kTinyTris && h->desc.num_meshes > 0 && h->desc.env_emitter < 0) {
-        tri_mesh.resize((size_t) T);
-        HIP_TRY(copy_on_stream(tri_mesh.data(), h->desc.tri_mesh, tri_mesh.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        forest = ForestBuilder::eligible(tri_mesh.data(), T, h->desc.num_meshes) && (!PSDR_FOREST_LDS_TABLES || small_tables_fit(h));
-    }
-    Builder b;
-    ForestBuilder fb;
-    b.kMaxLeaf = fb.max_leaf = h->opt.bvh_maxleaf; b.kTraversalCost = fb.traversal_cost = h->opt.bvh_tcost;
-    std::vector<float4> top_prims;
-    int32_t root = 0;
-    if (forest) {
-        if (const char *err = fb.run(rows.data(), tri_mesh.data(), T, h->desc.num_meshes)) return fail(err);
-        pack_tiny_prims(fb.inline_tris, top_prims);
-        // too many inline primitives: one tree.  Too few: nothing room-like to keep out of the trees (two bunnies and a light quad:
-        // PathTracer(3) 2.9 ms on one tree against 3.1 on the forest) -- the two-level tree is for walls around objects
-        if ((int) top_prims.size() / 3 > kTinyTris || (int) fb.inline_tris.size() / 3 < h->forest_min_inline) { forest = false; fb = ForestBuilder(); }
-    }
-    if (!forest) { if (const char *err = b.run(rows.data(), T, root)) return fail(err); }
-    std::vector<BvhNode> &nodes = forest ? fb.nodes : b.nodes;
-    std::vector<float4> &btris = forest ? fb.btris : b.btris;
-    if (nodes.size() > h->cap_nodes) {
-        if (h->d_nodes) (void) hipFree(h->d_nodes);
-        h->cap_nodes = std::max<size_t>(nodes.size(), 16);
-        HIP_TRY(hipMalloc(&h->d_nodes, h->cap_nodes * sizeof(BvhNode)));
-    }
-    if (btris.size() > h->cap_btris) {
-        if (h->d_btris) (void) hipFree(h->d_btris);
-        h->cap_btris = btris.size();
-        HIP_TRY(hipMalloc(&h->d_btris, h->cap_btris * sizeof(float4)));
-    }
-    if (!nodes.empty()) HIP_TRY(hipMemcpyAsync(h->d_nodes, nodes.data(), nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_btris, btris.data(), btris.size() * sizeof(float4), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));     // host vectors die at return
-    {   // hot rows of the reverse-mode gradient cache: emitter triangles first, then by decreasing area
-        constexpr int kMaxHotRows = 200;
-        std::vector<int32_t> map((size_t) T, -1), tris;
-        auto add = [&](int t) { if (t >= 0 && t < T && map[t] < 0 && (int) tris.size() < kMaxHotRows) { map[t] = (int32_t) tris.size(); tris.push_back(t); } };
-        // a scene whose triangles travel in the kernel arguments caches EVERY row, slot = triangle: its kernels (flag kSceneTiny) address the
-        // row without the map, the range test and the global-atomic arm (DeviceSink::add_tri)
-        h->hot_identity = tiny;
-        if (tiny) for (int t = 0; t < T; ++t) add(t);
-        for (int e = 0; e < h->desc.num_emitters; ++e) {
-            const int32_t *ei = h->emitter_i.data() + (size_t) e * PSDR_EMITTER_I_STRIDE;
-            for (int f = 0; f < ei[2] && f < 64; ++f) add(ei[1] + f);
-        }
-        std::vector<int> by_area((size_t) T);
-        for (int i = 0; i < T; ++i) by_area[i] = i;
-        const int top = std::min(T, kMaxHotRows);
-        std::partial_sort(by_area.begin(), by_area.begin() + top, by_area.end(),
-                          [&](int a, int c) { return rows[(size_t) a * PSDR_TRI_STRIDE + 21] > rows[(size_t) c * PSDR_TRI_STRIDE + 21]; });
-        for (int i = 0; i < top; ++i) add(by_area[i]);
-        if ((size_t) T > h->hot_cap) {
-            if (h->d_hot_map) (void) hipFree(h->d_hot_map);
-            if (h->d_hot_tris) (void) hipFree(h->d_hot_tris);
-            h->hot_cap = (size_t) T;
-            HIP_TRY(hipMalloc(&h->d_hot_map, h->hot_cap * sizeof(int32_t)));
-            HIP_TRY(hipMalloc(&h->d_hot_tris, kMaxHotRows * sizeof(int32_t)));
-        }
-        HIP_TRY(copy_on_stream(h->d_hot_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(copy_on_stream(h->d_hot_tris, tris.data(), tris.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        h->hot_rows = (int) tris.size();
-    }
-    h->root = root;
-    h->bvh_depth = forest ? fb.max_depth : b.max_depth; h->num_nodes = (int) nodes.size(); h->num_btris = (int) btris.size() / 3;
-    if (int rc = bvh4_build(h, nodes, forest ? fb.roots : std::vector<int32_t>{root}, forest, s)) return rc;
-    h->have_bvh = true;
-    h->n_tiny = 0; h->aa_cnt = 0; h->n_blas = 0; h->n_inline = 0; h->have_occ = false; h->emit_rows = 0;
-    if (forest) {
-        h->n_tiny = tiny_plane_form(top_prims, h->tiny, h->tiny_meta, &h->aa_cnt, h->aa_enabled);
-        update_emit_rows(h);
-        h->n_inline = (int) fb.inline_ids.size();
-        h->n_blas = (int) fb.roots.size();
-        for (int k = 0; k < h->n_blas; ++k) {
-            float lo[3], hi[3];
-            fb.tree_box(k, lo, hi);
-            h->blas_lo[k] = float4{lo[0], lo[1], lo[2], 0.f}; h->blas_hi[k] = float4{hi[0], hi[1], hi[2], 0.f};
-            std::memcpy(&h->blas_lo[k].w, &fb.roots[(size_t) k], 4);
-        }
-        if (!h->d_top) HIP_TRY(hipMalloc(&h->d_top, sizeof(float4) * (kMaxInlineTris * 3 + 2 * kMaxBlas)));
-        if (!h->d_inline_ids) HIP_TRY(hipMalloc(&h->d_inline_ids, sizeof(int32_t) * kMaxInlineTris));
-        if (h->n_inline) HIP_TRY(copy_on_stream(h->d_inline_ids, fb.inline_ids.data(), sizeof(int32_t) * (size_t) h->n_inline, hipMemcpyHostToDevice, s));
-    } else if (tiny) {
-        std::vector<float4> prims;
-        std::vector<int> row_of_prim;
-        pack_tiny_prims(b.btris, prims);           // walls as parallelograms: half the tests
-        h->n_tiny = tiny_plane_form(prims, h->tiny, h->tiny_meta, &h->aa_cnt, h->aa_enabled, &row_of_prim);
-        update_emit_rows(h);
-        // occluder rows of the light rays (SceneView::occ): which primitives can lie between a triangle and an emitter triangle
-        h->have_occ = false;
-        if (T <= 32 && h->n_tiny <= 32) {
-            std::vector<char> is_em((size_t) T, 0);
-            for (int e = 0; e < h->desc.num_emitters; ++e) {
-                const int32_t *ei = h->emitter_i.data() + (size_t) e * PSDR_EMITTER_I_STRIDE;
-                for (int f = 0; f < ei[2]; ++f) if (ei[1] + f >= 0 && ei[1] + f < T) is_em[(size_t) (ei[1] + f)] = 1;
-            }
-            std::vector<uint32_t> occ;
-            if (h->opt.occ_rows != 0) tiny_occluder_rows(prims, row_of_prim, T, is_em, occ);
-            else occ.assign((size_t) T * T, 0xffffffffu);
-            if (occ.size() > h->occ_cap) {
-                if (h->d_occ) (void) hipFree(h->d_occ);
-                h->occ_cap = std::max<size_t>(occ.size(), 32 * 32);
-                HIP_TRY(hipMalloc(&h->d_occ, h->occ_cap * sizeof(uint32_t)));
-            }
-            HIP_TRY(copy_on_stream(h->d_occ, occ.data(), occ.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            h->have_occ = true;
-            h->occ_max_rows = 0;                                     // the most rows any (triangle, emitter triangle) entry names (psdr_scene_info)
-            for (int r = 0; r < T; ++r) for (int e = 0; e < T; ++e) if (is_em[(size_t) e]) h->occ_max_rows = std::max(h->occ_max_rows, (int) __builtin_popcount(occ[(size_t) r * T + e] & ((1u << h->n_tiny) - 1u)));
-        }
-    }
-    // what the refit path needs: the levels of the breadth-first node order, the padding, the reference area
-    h->tree_tris = T; h->refits_since_build = 0; h->num_builds++; h->bvh_pad = forest ? fb.pad : b.pad;
-    h->level_start.clear();
-    double area = 0.0;
-    auto node_area = [](const BvhNode &n) {
-        const float dx = std::max(n.hi0[0], n.hi1[0]) - std::min(n.lo0[0], n.lo1[0]), dy = std::max(n.hi0[1], n.hi1[1]) - std::min(n.lo0[1], n.lo1[1]),
-                    dz = std::max(n.hi0[2], n.hi1[2]) - std::min(n.lo0[2], n.lo1[2]);
-        return (double) (dx * dy + dy * dz + dz * dx);
-    };
-    if (forest) {
-        h->level_start = fb.level_start;
-        for (const BvhNode &n : nodes) area += node_area(n);
-    } else if (root >= 0) {
-        std::vector<int> depth(b.nodes.size(), 0);
-        for (size_t i = 0; i < b.nodes.size(); ++i) {
-            const BvhNode &n = b.nodes[i];
-            if (n.c0 >= 0) depth[n.c0] = depth[i] + 1;
-            if (n.c1 >= 0) depth[n.c1] = depth[i] + 1;
-            if (i == 0 || depth[i] != depth[i - 1]) h->level_start.push_back((int) i);
-            area += node_area(n);
-        }
-        h->level_start.push_back((int) b.nodes.size());
-    }
-    h->refit_ok = true;
-    if (forest) for (int32_t r : fb.roots) if (r < 0) h->refit_ok = false;     // k_gather_top reads the roots as nodes 0 .. n_blas-1
-    h->built_area = (float) area;
-    if (!h->d_refit_area) HIP_TRY(hipMalloc(&h->d_refit_area, sizeof(float)));
-    return 0;
 }
 
 int psdr_trace(psdr_scene_t h, int32_t m, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy,

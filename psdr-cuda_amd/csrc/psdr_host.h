@@ -311,6 +311,8 @@ struct psdr_scene_s {
 constexpr int kRayCounters = 64, kRayCounterStride = 16;     // d_counters: 64 counters, 128 bytes apart
 // wavefront streams and trace-request queues: 64 sub-streams / sub-queues, their counters on their own 128-byte lines (psdr_kernels.h)
 constexpr int kWfSub = 64, kWfCountStride = 32;
+// the dense trace kernel (psdr_hip.hip k_wf_trace): threads per workgroup, bytes per staged 4-wide node, stack entries per lane in LDS at most
+constexpr int kTraceBlock = 1024, kTraceNodeStride = 80, kTraceStackMax = 16;
 
 #define HIP_TRY(expr)                                                                              \
     do { hipError_t e_ = (expr); if (e_ != hipSuccess) return psdr_host::fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
@@ -344,6 +346,7 @@ int begin_call(psdr_scene_s *h, hipStream_t s);
 int primary_edge_order(psdr_scene_s *h, const LaunchCtx &cx, long long i0, long long n, const uint32_t **order, hipStream_t s);
 constexpr int kMaxRefits = 64;              // full SAH rebuild at least this often
 constexpr float kRefitAreaGrowth = 1.3f;    // ... or when the summed inner-box area grew by 30 %
+constexpr int kLbvhAutoTris = 1 << 18;      // tables from this size are built on the device (psdr_lbvh.h) unless the option bvh_build says otherwise
 
 // entry points of one kernel variant (one scene flag set)
 struct VariantOps {
@@ -396,3 +399,4 @@ const VariantOps *variant_ops_10();     // no tree, rough conductor
 }  // namespace psdr_host
 
 #include "psdr_plan.h"
+#include "psdr_tree_plan.h"

@@ -16,7 +16,6 @@
 #pragma once
 
 constexpr int kLbvhLeaf = 4;                       // triangles per leaf (the host builder's kMaxLeaf)
-constexpr int kLbvhAutoTris = 1 << 18;
 
 struct LbvhInfo { int32_t depth; float area; int32_t bad; float pad; };
 

@@ -1,5 +1,6 @@
 // hostcheck_plan.cpp -- TEST-ONLY harness: the launch planning of csrc/psdr_plan.h (pure host functions: grids, LDS plans, launch forms) run over hand-filled
-// scene handles, so that tests/test_launch_plan_host.py can check every rule where no GPU exists.  No HIP call is made and no device is opened; psdr_host::fail,
+// scene handles, so that tests/test_launch_plan_host.py can check every rule where no GPU exists; and the tree build and trace planning of csrc/psdr_tree_plan.h
+// (hostcheck_tree at the end, for tests/test_tree_plan_host.py).  No HIP call is made and no device is opened; psdr_host::fail,
 // which the product defines in psdr_hip.hip, is this file's own and keeps the message.  Never imported by the psdr_cuda package.
 #include "../../psdr-cuda_amd/csrc/psdr_host.h"
 
@@ -115,5 +116,102 @@ int hostcheck_plan_rev_camera(const PlanHandle *p, const psdr_render_opts *o, in
     out += put_ctx(cx2, out);
     put_layout(L, out);
     return rc;
+}
+
+// ---- tree build and trace planning (csrc/psdr_tree_plan.h), for tests/test_tree_plan_host.py and for tests/hostcheck/tree_plan_san.cpp, which runs the same entry
+// under the host sanitizers: ONE entry, numbers in, numbers out (every integer and every float32 the rules see is exact in a double).  Rules that read the handle
+// take TreeHandle's fields first.  Returns the count of numbers written to `out`, -1 for an unknown rule or too few numbers.
+struct TreeHandle {
+    double refit_enabled, tiny_enabled, two_level_enabled, refit_ok, tree_tris, num_nodes, refits_since_build, lbvh, built_area, bvh_device_mode, num_meshes, env_emitter,
+        forest_min_inline, num_nodes4, stack_need4, lds_limit, trace_wg2, num_cus, blocks_per_cu;
+};
+int hostcheck_tree(const char *what, const double *in, int n, double *out) {
+    const std::string w(what);
+    const double *end = in + n;
+    bool short_of = false;
+    auto next = [&]() { if (in >= end) { short_of = true; return 0.0; } return *in++; };
+    auto next_ints = [&](size_t count) { std::vector<int32_t> v; for (size_t i = 0; i < count && !short_of; ++i) v.push_back((int32_t) next()); return v; };
+    psdr_scene_s h;
+    if (w == "refit" || w == "kind" || w == "trace" || w == "probe") {
+        TreeHandle t;
+        if (n < (int) (sizeof(t) / sizeof(double))) return -1;
+        std::memcpy(&t, in, sizeof(t)); in += sizeof(t) / sizeof(double);
+        h.refit_enabled = t.refit_enabled != 0; h.tiny_enabled = t.tiny_enabled != 0; h.two_level_enabled = t.two_level_enabled != 0; h.refit_ok = t.refit_ok != 0;
+        h.tree_tris = (int) t.tree_tris; h.num_nodes = (int) t.num_nodes; h.refits_since_build = (int) t.refits_since_build; h.lbvh = t.lbvh != 0;
+        h.built_area = (float) t.built_area; h.bvh_device_mode = (int) t.bvh_device_mode; h.desc.num_meshes = (int) t.num_meshes; h.desc.env_emitter = (int) t.env_emitter;
+        h.forest_min_inline = (int) t.forest_min_inline; h.num_nodes4 = (int) t.num_nodes4; h.stack_need4 = (int) t.stack_need4; h.lds_limit = (int) t.lds_limit;
+        h.opt.trace_wg2 = (int) t.trace_wg2; h.num_cus = (int) t.num_cus; h.opt.blocks_per_cu = (int) t.blocks_per_cu;
+    }
+    int m = 0;
+    if (w == "mask") {          // num_emitters, env_emitter, T, words of emitter_i, emitter_i -> emit_rows wanted, the mask
+        h.desc.num_emitters = (int) next(); h.desc.env_emitter = (int) next();
+        const int T = (int) next();
+        h.emitter_i = next_ints((size_t) next());
+        out[m++] = emit_rows_wanted(&h) ? 1 : 0;
+        for (char c : emitter_triangle_mask(h.emitter_i, h.desc.num_emitters, T)) out[m++] = c;
+    } else if (w == "hot") {          // T, tiny, num_emitters, words of emitter_i, emitter_i, entries of by_area, by_area -> slot -> triangle
+        const int T = (int) next(), tiny = (int) next(), num_emitters = (int) next();
+        const std::vector<int32_t> emitter_i = next_ints((size_t) next()), by_area = next_ints((size_t) next());
+        for (int32_t t : hot_row_list(T, tiny != 0, emitter_i, num_emitters, by_area.data(), (int) by_area.size())) out[m++] = t;
+    } else if (w == "occ") {          // T, n_tiny, is_em [T], occ [T * T] -> occ_max_rows
+        const int T = (int) next(), n_tiny = (int) next();
+        const std::vector<int32_t> em = next_ints((size_t) T);
+        std::vector<uint32_t> occ;
+        for (int i = 0; i < T * T; ++i) occ.push_back((uint32_t) next());
+        if (!short_of) out[m++] = occluder_max_rows(occ, std::vector<char>(em.begin(), em.end()), T, n_tiny);
+    } else if (w == "levels") {          // root, nodes, per node lo0 hi0 lo1 hi1 (12 floats) c0 c1 -> area, level_start
+        const int32_t root = (int32_t) next();
+        std::vector<BvhNode> nodes((size_t) next());
+        for (BvhNode &nd : nodes) {
+            for (float *f : {nd.lo0, nd.hi0, nd.lo1, nd.hi1}) for (int k = 0; k < 3; ++k) f[k] = (float) next();
+            nd.c0 = (int32_t) next(); nd.c1 = (int32_t) next();
+        }
+        std::vector<int> levels{-7};          // (cleared by the rule)
+        out[m++] = short_of ? 0.0 : tree_levels_and_area(nodes, root, levels);
+        for (int l : levels) out[m++] = l;
+    } else if (w == "refit") {          // T, tiny, emitters_same, forest_stands, prev_area -> refit_candidate, refit_choice
+        const int T = (int) next(), tiny = (int) next(), same = (int) next(), stands = (int) next();
+        const float prev_area = (float) next();
+        out[m++] = refit_candidate(&h, T, tiny != 0) ? 1 : 0;
+        out[m++] = refit_choice(&h, same != 0, stands != 0, prev_area);
+    } else if (w == "inline_fits") {
+        out[m++] = refit_inline_fits((int) next()) ? 1 : 0;
+    } else if (w == "kind") {          // T, packed top primitives, inline triangles -> tiny_scene, device_build_wanted, forest_candidate, forest_kept
+        const int T = (int) next(), n_top = (int) next(), n_inline = (int) next();
+        const bool tiny = tiny_scene(&h, T);
+        out[m++] = tiny; out[m++] = device_build_wanted(&h, T, tiny); out[m++] = forest_candidate(&h, T); out[m++] = forest_kept(&h, n_top, n_inline);
+    } else if (w == "forest_stands") {          // n_blas, num_meshes, num_emitters, faces of emitter 0 -> forest_stands
+        h.n_blas = (int) next(); h.desc.num_meshes = (int) next(); h.desc.num_emitters = (int) next(); h.desc.env_emitter = -1;
+        h.desc.face_cmf = h.desc.face_pmf = g_table;
+        h.emitter_i.assign((size_t) std::max(h.desc.num_emitters, 0) * PSDR_EMITTER_I_STRIDE, 0);
+        const int faces = (int) next();
+        if (!h.emitter_i.empty()) h.emitter_i[2] = faces;
+        out[m++] = forest_stands(&h) ? 1 : 0;
+    } else if (w == "trace") {          // sub_cap -> the plan
+        const TracePlan p = plan_wf_trace(&h, (long long) next());
+        for (double v : {(double) p.wg2, (double) p.ovf, (double) p.S, (double) p.n_lnodes, (double) p.off_stack, (double) p.stack_entries, (double) p.grid, (double) p.dyn,
+                         (double) p.ovf_stride, (double) p.ovf_bytes}) out[m++] = v;
+    } else if (w == "probe") {          // slots, rays_per_slot, per_cu -> the plan
+        const long long slots = (long long) next();
+        const int rays = (int) next(), per_cu = (int) next();
+        const ProbePlan p = plan_probe_buffers(&h, slots, rays, per_cu);
+        for (double v : {(double) p.sub_cap, (double) p.cnt_bytes, (double) p.hit_bytes, (double) p.mask_bytes, (double) p.req_bytes, (double) p.total}) out[m++] = v;
+    } else if (w == "boxes") {          // n_blas, blas_root4 [kMaxBlas] -> lo.w and hi.w of every box as integers (lo.w = 100 + k, hi.w = -1 going in)
+        h.n_blas = (int) next();
+        for (int k = 0; k < kMaxBlas; ++k) {
+            h.blas_root4[k] = (int32_t) next();
+            const int32_t root = 100 + k, none = -1;
+            h.blas_lo[k] = float4{(float) k, 0.f, 0.f, 0.f}; h.blas_hi[k] = float4{(float) k + 1.f, 1.f, 1.f, 0.f};
+            std::memcpy(&h.blas_lo[k].w, &root, 4); std::memcpy(&h.blas_hi[k].w, &none, 4);
+        }
+        float4 lo[kMaxBlas], hi[kMaxBlas];
+        pack_blas_boxes(&h, lo, hi);
+        for (int k = 0; k < kMaxBlas; ++k) {
+            int32_t a, b;
+            std::memcpy(&a, &lo[k].w, 4); std::memcpy(&b, &hi[k].w, 4);
+            out[m++] = a; out[m++] = b; out[m++] = lo[k].x; out[m++] = hi[k].x;
+        }
+    } else return -1;
+    return short_of ? -1 : m;
 }
 }
