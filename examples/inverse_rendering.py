@@ -6,6 +6,7 @@
     python examples/inverse_rendering.py envmap       # recover the environment map's pixels under a metal bunny
     python examples/inverse_rendering.py svbrdf       # recover albedo and roughness maps of a quad from three flash photographs (CollocatedIntegrator)
     python examples/inverse_rendering.py svbrdf --normals     # ... of a quad with a bumpy normal map: albedo, roughness and normals
+    python examples/inverse_rendering.py svbrdf --normals --lights     # ... from ONE view under three lamps (PointLightIntegrator), beside the three-tilt run
     python examples/inverse_rendering.py svbrdf --height      # ... of a quad with a relief: albedo, roughness and a height map
     python examples/inverse_rendering.py shape        # recover a displaced sphere's vertices, one by one, through psdr_cuda.LargeSteps
 
@@ -104,7 +105,7 @@ SVBRDF_XML = """<scene version="0.5.0">
 </scene>"""
 
 
-def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False, height=False):
+def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False, height=False, lights=False):
     """A quad with map_res x map_res kd and roughness maps (MicrofacetBSDF, F0 known) photographed with a flash at the camera under three tilts -- one quad
     transformed three times, the maps shared.  The diffuse lobe is seen at every tilt, the specular lobe only near normal incidence, so the two maps separate by
     angle.  Adam on both maps from a flat start; the flash's intensity brings the pixel values (1 / distance^2 = 1e-6) to order 0.1.
@@ -112,11 +113,14 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
     the normal map, started flat.  Tilts about one axis leave the sign of the normal's component along that axis open, so the third view tilts about x.
     height (--height): the target quad carries a height map instead (texels in [0, 1], 2 world units per unit of height: slopes up to about 0.5 on the 16 x 16 cells of the
     160 x 160 quad) and the loop recovers kd, roughness and the height map, started flat, from a head-on view and one tilt about each axis.  A height field has one number per texel
-    and its slopes are integrable by construction; a constant offset cannot be observed, so the error is reported with each map's mean removed."""
+    and its slopes are integrable by construction; a constant offset cannot be observed, so the error is reported with each map's mean removed.
+    lights (--normals --lights): ONE camera, the quad head-on, and three lamps 120 degrees apart around the viewing axis, about 37 degrees off it
+    (PointLightIntegrator, one per lamp: photometric stereo) instead of three tilts under the flash.  Returns the final mean angular error of the normals, if any."""
     rng = np.random.default_rng(3)
     kd_true = rng.uniform(0.2, 0.8, (map_res * map_res, 3)).astype(np.float32)
     r_true = rng.uniform(0.3, 0.6, map_res * map_res).astype(np.float32)
     integ = psdr_cuda.CollocatedIntegrator(1e6)
+    integs = [integ] * 3
     if height:
         tilts = ((0.0, 0.0), (35.0, 0.0), (0.0, 35.0))          # head-on (the specular lobe: roughness), about y and about x (the sign of each slope)
         h_true = rng.uniform(0.0, 1.0, map_res * map_res).astype(np.float32)
@@ -124,6 +128,9 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
         tilts = ((35.0, 0.0), (-35.0, 0.0), (0.0, 35.0))          # (about y, about x)
         v_true = np.concatenate([rng.uniform(-0.35, 0.35, (map_res * map_res, 2)), np.ones((map_res * map_res, 1))], axis=1)
         n_true = ((v_true + 1.0) / 2.0).astype(np.float32)          # the image encoding: texel = (v + 1) / 2
+        if lights:
+            tilts = ((0.0, 0.0),) * 3
+            integs = [psdr_cuda.PointLightIntegrator((600.0 * np.cos(a), 125.0 + 600.0 * np.sin(a), 800.0), 1e6) for a in np.radians([0.0, 120.0, 240.0])]
 
     def view(tilt, spp_, kd, rough, nm=None, hm=None):
         sc = psdr_cuda.Scene()
@@ -143,7 +150,7 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
             b.height_scale = psdr_cuda.Bitmap1fD(2.0)
         return sc
     targets = []
-    for tilt in tilts:
+    for tilt, integ in zip(tilts, integs):
         ref = view(tilt, 256, Vector3fD(torch.as_tensor(kd_true, device="cuda")), FloatD(torch.as_tensor(r_true, device="cuda")),
                    Vector3fD(torch.as_tensor(n_true, device="cuda")) if normals else None, FloatD(torch.as_tensor(h_true, device="cuda")) if height else None)
         ref.configure()
@@ -184,7 +191,7 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
     for it in range(steps):
         opt.zero_grad()
         total = 0.0
-        for sc, target in zip(views, targets):
+        for sc, target, integ in zip(views, targets, integs):
             sc.configure()
             loss = ek.hmean(ek.hsum(ek.sqr(integ.renderD(sc) - Vector3fD._wrap(target))))
             ek.backward(loss)
@@ -198,6 +205,7 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
             print("  step %3d  loss %.5f  %s" % (it, total, report()))
     torch.cuda.synchronize()
     print("  %.1f ms per step (three views)" % ((time.perf_counter() - t0) / steps * 1e3))
+    return angle() if normals else None
 
 
 def icosphere(level):
@@ -258,6 +266,12 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "albedo"
     if which == "svbrdf" and "--height" in sys.argv[2:]:
         svbrdf(height=True)
+    elif which == "svbrdf" and "--normals" in sys.argv[2:] and "--lights" in sys.argv[2:]:
+        print("three tilts under the flash at the camera (CollocatedIntegrator):")
+        tilted = svbrdf(normals=True)
+        print("one view under three lamps (PointLightIntegrator):")
+        lit = svbrdf(normals=True, lights=True)
+        print("mean angular error of the normals: three lamps %.2f degrees, three tilts %.2f degrees" % (lit, tilted))
     elif which == "svbrdf" and "--normals" in sys.argv[2:]:
         svbrdf(normals=True)
     else:

@@ -119,6 +119,12 @@ extern "C" {
    one per primary-edge slot.  Gradients: interior + primary edges -- a point seen from the camera is seen from the light, so there is no secondary-edge
    term and sppse is ignored.  The caller scales image, derivative images and adjoint image by the light's RGB intensity. */
 #define PSDR_INTEGRATOR_COLLOCATED 3
+/* PointLightIntegrator (build-defined, csrc/psdr_pointlight.h): a point light of unit intensity at the world position psdr_scene_set_point_light gave
+   the handle.  For a camera ray that hits `its`, with dv = pL - its.p:  Li = f(its; wi = its.wi, wo = to_local(dv / |dv|)) * V(its.p, pL) / |dv|^2,
+   V = 0 if the ray from its.p towards pL meets a surface at t in [RayEpsilon, |dv| - ShadowEpsilon).  Emitters add nothing; draws per slot: 2 (camera),
+   1 (primary edge), 3 (shadow boundary, the first is used).  Gradients: interior + primary edges + the boundary of the moving shadow outline, which
+   honours sppse and its shard range.  A render call of this kind without a light set is an error.  The caller scales by the light's RGB intensity. */
+#define PSDR_INTEGRATOR_POINT 4
 /* FieldExtractionIntegrator fields (src/integrator/field.cpp:10-54) */
 #define PSDR_FIELD_SILHOUETTE 0
 #define PSDR_FIELD_POSITION   1
@@ -371,6 +377,10 @@ int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *opts,
    hmax(sum over the segment's camera connections of |value|) / reso[3].  At max_depth 1 the mass of segment 1 is
    psdr_guide_build's. */
 int psdr_scene_set_path_guide(psdr_scene_t h, const int32_t reso[3], const float *cmf, const float *pmf, float sum);
+/* The light of PSDR_INTEGRATOR_POINT.  pos: world position (host, copied).  d_pos: HOST array [K][3] of position tangents (copied; K = 0..3) or NULL --
+   psdr_render_d_fwd reads the first K' rows of its own K, missing rows are zero.  g_pos: DEVICE array [3] that psdr_render_d_rev adds the gradient of
+   the position into (+=; the caller zeroes it and keeps it alive), or NULL.  pos == NULL removes the light.  The light survives psdr_scene_set_tables. */
+int psdr_scene_set_point_light(psdr_scene_t h, const float pos[3], int32_t K, const float *d_pos, float *g_pos);
 int psdr_path_guide_build(psdr_scene_t h, const psdr_render_opts *opts, int32_t segment,
                           const int32_t reso[4], int32_t nrounds,
                           float *out_mass, void *stream);

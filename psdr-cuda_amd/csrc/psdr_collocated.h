@@ -40,9 +40,16 @@ PSDR_HD Vec3<M> collocated_camera_sample(const SceneView &sc, const TVT &tv, Tra
 
 // One primary-edge slot up to the difference of Li across the edge (primary_edge_sample / primary_edge_reverse_values with this estimator): what forward and
 // reverse mode share.  false: the slot contributes nothing.
+// LiOf: the estimator on the two sides, at<KNOWN>(...) = Li of one camera ray -- this integrator's, or the PointLightIntegrator's (psdr_pointlight.h)
 struct CollocatedEdge { int k, pixel; float u, nx, ny, xdn; float dL[3]; };
-template <int FL>
-PSDR_HD bool collocated_edge_values(const SceneView &sc, TraversalStack &st, const RngJump &jump, uint64_t slot, uint32_t &nrays, CollocatedEdge &e) {
+struct CollocatedLi {
+    template <bool KNOWN, class TVT>
+    PSDR_HD Vec3f at(const SceneView &sc, const TVT &tv0, TraversalStack &st, const RayT<float> &ray, bool active, uint32_t &nrays, const Hit *primary) const {
+        return li_collocated<float, float, KNOWN>(sc, tv0, st, ray, active, nrays, primary);
+    }
+};
+template <int FL, class LiOf = CollocatedLi>
+PSDR_HD bool collocated_edge_values(const SceneView &sc, TraversalStack &st, const RngJump &jump, uint64_t slot, uint32_t &nrays, CollocatedEdge &e, const LiOf &li = LiOf()) {
     Rng rng; rng.init(slot, jump);
     float u = rng.next(), pmf;
     const int k = sample_reuse(sc.d.prim_cmf, sc.d.prim_pmf, sc.d.prim_sum, sc.d.num_prim_edges, u, pmf);
@@ -65,8 +72,14 @@ PSDR_HD bool collocated_edge_values(const SceneView &sc, TraversalStack &st, con
         const float sg = side == 0 ? -kEdgeEpsilon : kEdgeEpsilon;
         const RayT<float> ray = primary_ray<float>(sc, tv0, px + sg * nx, py + sg * ny);
         Vec3f L;
-        if constexpr (pair_walk_ok<FL>()) { const Hit hs = side == 0 ? hp0 : hp1; L = li_collocated<float, float, true>(sc, tv0, st, ray, valid, nrays, &hs); }
-        else L = li_collocated<float, float>(sc, tv0, st, ray, valid, nrays);
+        // (this integrator's own Li is called as it always was: through the functor the two-level rough unit compiled to other code)
+        if constexpr (std::is_same<LiOf, CollocatedLi>::value) {
+            if constexpr (pair_walk_ok<FL>()) { const Hit hs = side == 0 ? hp0 : hp1; L = li_collocated<float, float, true>(sc, tv0, st, ray, valid, nrays, &hs); }
+            else L = li_collocated<float, float>(sc, tv0, st, ray, valid, nrays);
+        } else {
+            if constexpr (pair_walk_ok<FL>()) { const Hit hs = side == 0 ? hp0 : hp1; L = li.template at<true>(sc, tv0, st, ray, valid, nrays, &hs); }
+            else L = li.template at<false>(sc, tv0, st, ray, valid, nrays, nullptr);
+        }
         if (side == 0) Ln = L; else Lp = L;
     }
     if (!valid) return false;
@@ -75,11 +88,11 @@ PSDR_HD bool collocated_edge_values(const SceneView &sc, TraversalStack &st, con
     return true;
 }
 // forward mode: returns the pixel (or -1), tan[k][c] = d value / d P_k
-template <int K, int FL>
+template <int K, int FL, class LiOf = CollocatedLi>
 PSDR_HD int collocated_edge_sample(const SceneView &sc, const TangentView<K, FL> &tv, TraversalStack &st, const RngJump &jump, uint64_t slot, float inv_sppe,
-                                   float tan[K][3], uint32_t &nrays) {
+                                   float tan[K][3], uint32_t &nrays, const LiOf &li = LiOf()) {
     CollocatedEdge e;
-    if (!collocated_edge_values<FL>(sc, st, jump, slot, nrays, e)) return -1;
+    if (!collocated_edge_values<FL>(sc, st, jump, slot, nrays, e, li)) return -1;
     const bool fin[3] = {isfinite(e.xdn * e.dL[0]), isfinite(e.xdn * e.dL[1]), isfinite(e.xdn * e.dL[2])};
 #pragma unroll
     for (int t = 0; t < K; ++t) {
@@ -91,12 +104,12 @@ PSDR_HD int collocated_edge_sample(const SceneView &sc, const TangentView<K, FL>
     return e.pixel;
 }
 // reverse mode: returns the edge (or -1) and w[4] = the gradient of its (p0.x, p0.y, p1.x, p1.y) words
-template <int FL>
+template <int FL, class LiOf = CollocatedLi>
 PSDR_HD int collocated_edge_reverse_values(const SceneView &sc, TraversalStack &st, const RngJump &jump, uint64_t slot, float inv_sppe,
-                                           const float *__restrict__ adj_img, uint32_t &nrays, float w[4]) {
+                                           const float *__restrict__ adj_img, uint32_t &nrays, float w[4], const LiOf &li = LiOf()) {
     w[0] = w[1] = w[2] = w[3] = 0.f;
     CollocatedEdge e;
-    if (!collocated_edge_values<FL>(sc, st, jump, slot, nrays, e)) return -1;
+    if (!collocated_edge_values<FL>(sc, st, jump, slot, nrays, e, li)) return -1;
     const float *a = adj_img + (size_t) e.pixel * 3;
     float g = 0.f;
 #pragma unroll

@@ -489,7 +489,7 @@ void fill_top(const psdr_scene_s *h, SceneView &sc) {
 int make_ctx(psdr_scene_s *h, const psdr_render_opts *o, int sampler, LaunchCtx &cx) {
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (!h->have_bvh) return fail("Input scene must be configured!");
-    if (o->integrator != PSDR_INTEGRATOR_FIELD && o->integrator != PSDR_INTEGRATOR_COLLOCATED && h->desc.num_emitters <= 0) return fail("No Emitter!");
+    if (o->integrator != PSDR_INTEGRATOR_FIELD && o->integrator != PSDR_INTEGRATOR_COLLOCATED && o->integrator != PSDR_INTEGRATOR_POINT && h->desc.num_emitters <= 0) return fail("No Emitter!");
     if (o->integrator == PSDR_INTEGRATOR_DIRECT && !(o->bsdf_samples >= 0 && o->light_samples >= 0 && o->bsdf_samples + o->light_samples > 0))
         return fail("DirectIntegrator: bsdf_samples + light_samples must be positive");
     cx.sc.d = h->desc; cx.sc.nodes = h->d_nodes; cx.sc.btris = h->d_btris; cx.sc.root = h->root;
@@ -797,7 +797,7 @@ int probe_buffers(psdr_scene_s *h, long long slots, int rays_per_slot, ProbeBuff
     return 0;
 }
 
-// kernel variant of the scene (scene_flag_set), and the same choice for the kernels of psdr_path_sedge.hip and of psdr_collocated.hip
+// kernel variant of the scene (scene_flag_set), and the same choice for the kernels of psdr_path_sedge.hip, of psdr_collocated.hip and of psdr_pointlight.hip
 #define PSDR_OPS_OF(OPS)                                                                                                              \
     switch (scene_flag_set(h)) {                                                                                                      \
         case 0: return OPS##0(); case 1: return OPS##1(); case 2: return OPS##2(); case 3: return OPS##3();                          \
@@ -807,6 +807,12 @@ int probe_buffers(psdr_scene_s *h, long long slots, int rays_per_slot, ProbeBuff
 const VariantOps *variant_of(const psdr_scene_s *h) { PSDR_OPS_OF(variant_ops_) }
 const PathSedgeOps *path_sedge_of(const psdr_scene_s *h) { PSDR_OPS_OF(path_sedge_ops_) }
 const CollocatedOps *collocated_of(const psdr_scene_s *h) { PSDR_OPS_OF(collocated_ops_) }
+const PointLightOps *point_light_of(const psdr_scene_s *h) { PSDR_OPS_OF(point_light_ops_) }
+// PSDR_INTEGRATOR_POINT without a light: an error before any launch
+int check_point_light(const psdr_scene_s *h, const psdr_render_opts *o) {
+    if (o->integrator == PSDR_INTEGRATOR_POINT && !h->have_point) return fail("PointLightIntegrator: no light set (psdr_scene_set_point_light)");
+    return 0;
+}
 #undef PSDR_OPS_OF
 }  // namespace psdr_host
 using namespace psdr_host;
@@ -1196,12 +1202,14 @@ int psdr_render_c(psdr_scene_t h, const psdr_render_opts *o, float *out_img, voi
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (int rc = check_counts(h, o)) return rc;
     if (int rc = check_microfacet(h, o)) return rc;
+    if (int rc = check_point_light(h, o)) return rc;
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
     if (o->integrator == PSDR_INTEGRATOR_PATH) h->last_path_depth = o->max_depth;
     const long long WH = (long long) h->desc.width * h->desc.height;
     HIP_TRY(hipMemsetAsync(out_img, 0, sizeof(float) * WH * 3, s));
     if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_c(h, o, out_img, s);
+    if (o->integrator == PSDR_INTEGRATOR_POINT) return point_light_of(h)->render_c(h, o, out_img, s);
     return variant_of(h)->render_c(h, o, out_img, s);
 }
 
@@ -1212,9 +1220,11 @@ int psdr_render_d_fwd(psdr_scene_t h, const psdr_render_opts *o, int32_t K, cons
     if (int rc = check_counts(h, o)) return rc;
     if (int rc = check_microfacet(h, o)) return rc;
     if (int rc = check_path_sedges(o)) return rc;
+    if (int rc = check_point_light(h, o)) return rc;
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
     if (K != 1 && K != 3) return fail("psdr_render_d_fwd: K must be 1 or 3");
+    if (o->integrator == PSDR_INTEGRATOR_POINT) return point_light_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s);          // interior + primary edges + shadow boundary
     if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s);          // interior + primary edges: no secondary-edge term
     if (int rc = variant_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s)) return rc;
     return path_sedge_of(h)->fwd(h, o, K, tangents, out_dimg, s);          // PSDR_FLAG_PATH_SEDGES (nothing without it)
@@ -1227,6 +1237,7 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
     if (int rc = check_counts(h, o)) return rc;
     if (int rc = check_microfacet(h, o)) return rc;
     if (int rc = check_path_sedges(o)) return rc;
+    if (int rc = check_point_light(h, o)) return rc;
     if (o->flags & PSDR_FLAG_LITERAL_FORMS) return fail("psdr_render_d_rev: PSDR_FLAG_LITERAL_FORMS is a forward-mode diagnostic (no literal-form adjoint)");
     if (o->integrator == PSDR_INTEGRATOR_PATH && o->max_depth > kMaxRevDepthDeep)
         return fail("psdr_render_d_rev: PathTracer max_depth > 250 is not supported in reverse mode");
@@ -1235,8 +1246,23 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
     std::fill(std::begin(h->rev_layout), std::end(h->rev_layout), 0);
     h->rev_layout[8] = -1;                                                // (no camera launch)
     if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_rev(h, o, adj_img, out_img, grads, s);
+    if (o->integrator == PSDR_INTEGRATOR_POINT) return point_light_of(h)->render_rev(h, o, adj_img, out_img, grads, s);
     if (int rc = variant_of(h)->render_rev(h, o, adj_img, out_img, grads, s)) return rc;
     return path_sedge_of(h)->rev(h, o, adj_img, grads, s);                 // PSDR_FLAG_PATH_SEDGES (nothing without it)
+}
+
+int psdr_scene_set_point_light(psdr_scene_t h, const float pos[3], int32_t K, const float *d_pos, float *g_pos) {
+    if (!h) return fail("psdr_scene_set_point_light: null handle");
+    if (K < 0 || K > 3) return fail("psdr_scene_set_point_light: K must be 0..3");
+    if (pos != nullptr && !(std::isfinite(pos[0]) && std::isfinite(pos[1]) && std::isfinite(pos[2]))) return fail("psdr_scene_set_point_light: the position is not finite");
+    h->have_point = pos != nullptr;
+    h->point_K = 0; h->point_gpos = nullptr;
+    std::memset(h->point_dpos, 0, sizeof(h->point_dpos));
+    if (pos == nullptr) return 0;
+    for (int c = 0; c < 3; ++c) h->point_pos[c] = pos[c];
+    if (d_pos != nullptr) { h->point_K = K; std::memcpy(h->point_dpos, d_pos, sizeof(float) * 3 * (size_t) K); }
+    h->point_gpos = g_pos;
+    return 0;
 }
 
 int psdr_guide_build(psdr_scene_t h, const psdr_render_opts *o, const int32_t reso[4], int32_t nrounds, float *out_mass, void *stream) {

@@ -305,7 +305,12 @@ struct psdr_scene_s {
     int32_t pg_reso[3] = {1, 1, 1};
     const float *pg_cmf = nullptr, *pg_pmf = nullptr;
     float pg_sum = 0.f;
-    bool has_microfacet = false;           // desc.material_mask announces a MicrofacetBSDF (PSDR_BSDF_MICROFACET): CollocatedIntegrator only
+    bool has_microfacet = false;           // desc.material_mask announces a MicrofacetBSDF (PSDR_BSDF_MICROFACET): CollocatedIntegrator / PointLightIntegrator only
+    // the light of PSDR_INTEGRATOR_POINT (psdr_scene_set_point_light): position, K tangents of it (forward mode), the caller's device gradient (reverse mode)
+    bool have_point = false;
+    float point_pos[3] = {0.f, 0.f, 0.f}, point_dpos[3][3] = {};
+    int point_K = 0;
+    float *point_gpos = nullptr;
 };
 
 constexpr int kRayCounters = 64, kRayCounterStride = 16;     // d_counters: 64 counters, 128 bytes apart
@@ -384,6 +389,20 @@ const CollocatedOps *collocated_ops_4();
 const CollocatedOps *collocated_ops_6();
 const CollocatedOps *collocated_ops_8();
 const CollocatedOps *collocated_ops_10();
+// The PointLightIntegrator (PSDR_INTEGRATOR_POINT, psdr_pointlight.h) per flag set: psdr_pointlight.hip, one more translation unit per set, picked like CollocatedOps
+struct PointLightOps {
+    int (*render_c)(psdr_scene_s *h, const psdr_render_opts *o, float *img, hipStream_t s);
+    int (*render_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s);
+    int (*render_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, hipStream_t s);
+};
+const PointLightOps *point_light_ops_0();
+const PointLightOps *point_light_ops_1();
+const PointLightOps *point_light_ops_2();
+const PointLightOps *point_light_ops_3();
+const PointLightOps *point_light_ops_4();
+const PointLightOps *point_light_ops_6();
+const PointLightOps *point_light_ops_8();
+const PointLightOps *point_light_ops_10();
 // The lean twin of the K = 1 log-derivative camera kernel for flag set 8 (psdr_logd_lean.hip): launches it behind the gate kernels of run_camera and
 // sets *ran, or leaves *ran false -- option logd_park 0, or the parking columns do not fit six workgroups per CU (or a forced lds_budget) -- and
 // run_camera launches k_camera_logd.  cx: the launch context of run_camera (off_park is set on a copy).

@@ -614,3 +614,155 @@ class CollocatedIntegrator(Integrator):
             torch.cuda.synchronize()
             self.log("Rendered in %g seconds." % (time.perf_counter() - t0))
         return img
+
+
+class _PointRenderFn(torch.autograd.Function):
+    """torch.autograd bridge of the PointLightIntegrator's reverse mode: _RenderFn with one more input, the light position, whose gradient
+    psdr_render_d_rev adds into a device array of three floats."""
+
+    @staticmethod
+    def forward(ctx, node, pos, *inputs):
+        ctx.node, ctx.present, ctx.pos_shape = node, [t is not None for t in inputs], pos.shape
+        unit = node.unit
+        with _decided(unit.collective), unit.integrator._light(node.pos):
+            img = unit.integrator._render_c(unit.scene, unit.tb, unit.opts, unit.guide, interior_only=True)
+        return img.reshape(-1, 3)
+
+    @staticmethod
+    def backward(ctx, adj):
+        node, unit = ctx.node, ctx.node.unit
+        g_pos = torch.zeros(3, dtype=torch.float32, device="cuda") if ctx.needs_input_grad[1] else None
+        with _decided(unit.collective), unit.integrator._light(node.pos, g_pos=g_pos):
+            grads = unit.integrator._render_rev(unit.scene, unit.tb, unit.opts, unit.guide, adj.contiguous().reshape(-1))
+            dist = _dist()
+            if dist and g_pos is not None:
+                dist.all_reduce(g_pos)
+            unit.integrator._forget_light(unit.scene)          # the handle must not keep the address of g_pos beyond this call
+        out = [None, g_pos.reshape(ctx.pos_shape) if g_pos is not None else None]
+        for k, present in zip(_AD_KEYS, ctx.present):
+            out.append(grads.get(k) if present else None)
+        return tuple(out)
+
+
+class _PointLightNode(_CollocatedNode):
+    """renderD of the PointLightIntegrator: _CollocatedNode with a ninth input, the light position (its value at the renderD call is the one every
+    deferred launch of the node uses)."""
+
+    def __init__(self, unit, intensity, position):
+        super().__init__(unit, intensity)
+        self.position = position
+        self.pos = [float(x) for x in position.t.detach().reshape(-1).cpu()]
+
+    def input_tensors(self):
+        return super().input_tensors() + [self.position.t]
+
+    def render_forward(self, tangents):
+        d_pos = None if tangents[-1] is None else [float(x) for x in tangents[-1].detach().reshape(-1).cpu()]
+        with self.unit.integrator._light(self.pos, d_pos=d_pos):
+            return super().render_forward(list(tangents[:-1]))
+
+    def render_primal(self):
+        unit, inputs = self.unit, self.unit.input_tensors()
+        with torch.enable_grad():
+            pos = self.position.t
+            if pos.requires_grad or any(t is not None and t.requires_grad for t in inputs):
+                img = _PointRenderFn.apply(self, pos, *inputs)
+            else:
+                with _decided(unit.collective), unit.integrator._light(self.pos):
+                    img = unit.integrator._render_c(unit.scene, unit.tb, unit.opts, unit.guide, interior_only=True).reshape(-1, 3)
+            return img * self.intensity.t.reshape(1, 3).to(img.device)
+
+
+class _light_scope:
+    def __init__(self, integrator, pos, d_pos, g_pos):
+        self.integrator, self.state = integrator, (pos, d_pos, g_pos)
+
+    def __enter__(self):
+        self.saved, self.integrator._light_state = self.integrator._light_state, self.state
+        return self
+
+    def __exit__(self, *exc):
+        self.integrator._light_state = self.saved
+        return False
+
+
+class PointLightIntegrator(CollocatedIntegrator):
+    """A point light at an arbitrary, differentiable world position: the set-up of photometric stereo, of a light stage, of a camera with an off-axis
+    flash.  NOT in the reference snapshot: build-defined, like the CollocatedIntegrator it generalises.  For a camera ray that hits `its`, with the
+    light at pL, dv = pL - its.p and r = |dv|
+
+        Li = intensity * f(its; wi = its.wi, wo = to_local(dv / r)) * V(its.p, pL) / r^2          (0 on a miss)
+
+    with f the BSDF value, cosine included (Diffuse, RoughConductor, MicrofacetBSDF with or without a normal or height map) and V the visibility of the
+    light.  Emitters in the scene add nothing and a scene without any emitter is valid.  renderD's geometry gradient has three terms: the interior,
+    the primary edges (scene.opts.sppe) and the boundary of the moving shadow outline (scene.opts.sppse slots of the secondary-edge table).
+
+    position: three floats or a Vector3fD, kept as the differentiable attribute m_position; intensity: as CollocatedIntegrator's, m_intensity.  Both
+    take part in enoki.forward and enoki.backward.  The kernels render ONE light of unit intensity (csrc/psdr_pointlight.h): several lights are
+    several integrators whose images add."""
+    _type_name = "PointLightIntegrator"
+    _kind = _abi.INTEGRATOR_POINT
+
+    def __init__(self, position, intensity=1.0):
+        super().__init__(intensity)
+        if isinstance(position, Vector3fD):
+            psdr_assert(tuple(position.t.shape) == (1, 3), "position: one point expected")
+            self.m_position = position
+        else:
+            v = [float(x) for x in np.asarray(position, dtype=np.float64).reshape(-1)]
+            psdr_assert(len(v) == 3 and all(np.isfinite(v)), "position: three finite floats expected")
+            self.m_position = Vector3fD(v)
+        self._light_state = None
+
+    def _light(self, pos, d_pos=None, g_pos=None):
+        """the light every native call inside the block renders with (position, its tangent in forward mode, its device gradient in reverse mode)"""
+        return _light_scope(self, pos, d_pos, g_pos)
+
+    def _opts(self, scene, with_edges):
+        opts = super()._opts(scene, with_edges)
+        if with_edges and scene.opts.sppse > 0:          # the shadow boundary: sppse slots, sharded like the other samplers
+            dist = _dist()
+            rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
+            opts.sppse = scene.opts.sppse
+            opts.sppse_begin, opts.sppse_end = shard_range(opts.sppse, rank, world)
+        return opts
+
+    def _prepare(self, scene, tb, guide):
+        lib, keep = super()._prepare(scene, tb, guide)
+        psdr_assert(self._light_state is not None, "PointLightIntegrator: no light in scope")
+        pos, d_pos, g_pos = self._light_state
+        _abi.check(lib, lib.psdr_scene_set_point_light(scene._native, (C.c_float * 3)(*pos), 0 if d_pos is None else 1,
+                                                       None if d_pos is None else (C.c_float * 3)(*d_pos), None if g_pos is None else g_pos.data_ptr()))
+        if g_pos is not None:
+            keep.append(g_pos)
+        return lib, keep
+
+    def _forget_light(self, scene):
+        """removes the light from the scene's handle (with it the tangent and the gradient address of the last call); the next native call sets its own"""
+        if scene._native is not None:
+            lib = _abi.load_hip()
+            _abi.check(lib, lib.psdr_scene_set_point_light(scene._native, None, 0, None, None))
+
+    def renderC(self, scene, sensor_id=0):
+        with self._light([float(x) for x in self.m_position.t.detach().reshape(-1).cpu()]):
+            return super().renderC(scene, sensor_id)
+
+    def renderD(self, scene, sensor_id=0):
+        self._check_bsdfs(scene)
+        psdr_assert(scene.is_ready(), "Input scene must be configured!")
+        psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")
+        t0 = time.perf_counter()
+        tb = scene.tables(sensor_id, capacity=True)
+        opts = self._opts(scene, with_edges=True)
+        if not (scene._sensor_tables[sensor_id]["num_prim_edges"] > 0):
+            opts.sppe = opts.sppe_begin = opts.sppe_end = 0
+        if not (tb.get("num_sec_edges", 0) > 0):
+            opts.sppse = opts.sppse_begin = opts.sppse_end = 0
+        img = _CollocatedImage._make(_PointLightNode(_RenderNode(self, scene, sensor_id, tb, opts, None), self.m_intensity, self.m_position))
+        self._advance_rng(scene, opts)
+        ek.register_render_node(img)
+        if scene.opts.log_level:
+            img.t                                        # (the log line reports the render's time)
+            torch.cuda.synchronize()
+            self.log("Rendered in %g seconds." % (time.perf_counter() - t0))
+        return img
