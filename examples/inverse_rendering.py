@@ -7,6 +7,7 @@
     python examples/inverse_rendering.py svbrdf       # recover albedo and roughness maps of a quad from three flash photographs (CollocatedIntegrator)
     python examples/inverse_rendering.py svbrdf --normals     # ... of a quad with a bumpy normal map: albedo, roughness and normals
     python examples/inverse_rendering.py svbrdf --normals --lights     # ... from ONE view under three lamps (PointLightIntegrator), beside the three-tilt run
+    python examples/inverse_rendering.py svbrdf --normals --lights --stack     # ... and with the three lamps as one LightStageIntegrator: ms per step of both
     python examples/inverse_rendering.py svbrdf --height      # ... of a quad with a relief: albedo, roughness and a height map
     python examples/inverse_rendering.py shape        # recover a displaced sphere's vertices, one by one, through psdr_cuda.LargeSteps
 
@@ -105,7 +106,7 @@ SVBRDF_XML = """<scene version="0.5.0">
 </scene>"""
 
 
-def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False, height=False, lights=False):
+def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False, height=False, lights=False, stack=False):
     """A quad with map_res x map_res kd and roughness maps (MicrofacetBSDF, F0 known) photographed with a flash at the camera under three tilts -- one quad
     transformed three times, the maps shared.  The diffuse lobe is seen at every tilt, the specular lobe only near normal incidence, so the two maps separate by
     angle.  Adam on both maps from a flat start; the flash's intensity brings the pixel values (1 / distance^2 = 1e-6) to order 0.1.
@@ -115,7 +116,9 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
     160 x 160 quad) and the loop recovers kd, roughness and the height map, started flat, from a head-on view and one tilt about each axis.  A height field has one number per texel
     and its slopes are integrable by construction; a constant offset cannot be observed, so the error is reported with each map's mean removed.
     lights (--normals --lights): ONE camera, the quad head-on, and three lamps 120 degrees apart around the viewing axis, about 37 degrees off it
-    (PointLightIntegrator, one per lamp: photometric stereo) instead of three tilts under the flash.  Returns the final mean angular error of the normals, if any."""
+    (PointLightIntegrator, one per lamp: photometric stereo) instead of three tilts under the flash.
+    stack (--normals --lights --stack): the three lamps as ONE LightStageIntegrator -- one renderD and one backward per step, the three photographs are the planes
+    of its image.  Returns the final mean angular error of the normals, if any (with lights: that and the ms per step)."""
     rng = np.random.default_rng(3)
     kd_true = rng.uniform(0.2, 0.8, (map_res * map_res, 3)).astype(np.float32)
     r_true = rng.uniform(0.3, 0.6, map_res * map_res).astype(np.float32)
@@ -130,7 +133,10 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
         n_true = ((v_true + 1.0) / 2.0).astype(np.float32)          # the image encoding: texel = (v + 1) / 2
         if lights:
             tilts = ((0.0, 0.0),) * 3
-            integs = [psdr_cuda.PointLightIntegrator((600.0 * np.cos(a), 125.0 + 600.0 * np.sin(a), 800.0), 1e6) for a in np.radians([0.0, 120.0, 240.0])]
+            lamps = [(600.0 * np.cos(a), 125.0 + 600.0 * np.sin(a), 800.0) for a in np.radians([0.0, 120.0, 240.0])]
+            integs = [psdr_cuda.PointLightIntegrator(p, 1e6) for p in lamps]
+            if stack:
+                tilts, integs = ((0.0, 0.0),), [psdr_cuda.LightStageIntegrator(lamps, 1e6)]
 
     def view(tilt, spp_, kd, rough, nm=None, hm=None):
         sc = psdr_cuda.Scene()
@@ -194,6 +200,8 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
         for sc, target, integ in zip(views, targets, integs):
             sc.configure()
             loss = ek.hmean(ek.hsum(ek.sqr(integ.renderD(sc) - Vector3fD._wrap(target))))
+            if stack:
+                loss = loss * 3.0          # the mean over the stack's three planes: three times that is the sum of the three lamps' means
             ek.backward(loss)
             total += float(loss.t.item())
         opt.step()
@@ -204,7 +212,10 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
         if it % 10 == 0 or it == steps - 1:
             print("  step %3d  loss %.5f  %s" % (it, total, report()))
     torch.cuda.synchronize()
-    print("  %.1f ms per step (three views)" % ((time.perf_counter() - t0) / steps * 1e3))
+    ms = (time.perf_counter() - t0) / steps * 1e3
+    print("  %.1f ms per step (%s)" % (ms, "one stack of three lamps" if stack else "three views"))
+    if lights:
+        return angle(), ms
     return angle() if normals else None
 
 
@@ -270,8 +281,13 @@ if __name__ == "__main__":
         print("three tilts under the flash at the camera (CollocatedIntegrator):")
         tilted = svbrdf(normals=True)
         print("one view under three lamps (PointLightIntegrator):")
-        lit = svbrdf(normals=True, lights=True)
+        lit, lit_ms = svbrdf(normals=True, lights=True)
         print("mean angular error of the normals: three lamps %.2f degrees, three tilts %.2f degrees" % (lit, tilted))
+        if "--stack" in sys.argv[2:]:
+            print("one view under three lamps as one stack (LightStageIntegrator):")
+            stacked, stacked_ms = svbrdf(normals=True, lights=True, stack=True)
+            print("three lamps: one LightStageIntegrator %.1f ms per step (normals %.2f degrees), three PointLightIntegrators %.1f ms per step (normals %.2f degrees)" %
+                  (stacked_ms, stacked, lit_ms, lit))
     elif which == "svbrdf" and "--normals" in sys.argv[2:]:
         svbrdf(normals=True)
     else:

@@ -125,6 +125,13 @@ extern "C" {
    1 (primary edge), 3 (shadow boundary, the first is used).  Gradients: interior + primary edges + the boundary of the moving shadow outline, which
    honours sppse and its shard range.  A render call of this kind without a light set is an error.  The caller scales by the light's RGB intensity. */
 #define PSDR_INTEGRATOR_POINT 4
+/* LightStageIntegrator (build-defined, csrc/psdr_lightstage.h): the L point lights psdr_scene_set_point_lights gave the handle, each of unit intensity,
+   rendered from ONE camera hit per sample slot.  Plane l of every image is PSDR_INTEGRATOR_POINT's image under light l at the same options (same draws,
+   same rng_offset for every light): psdr_render_c overwrites out_img [L][H*W*3]; psdr_render_d_fwd writes out_img [L][H*W*3] and out_dimg [K][L][H*W*3];
+   psdr_render_d_rev reads adj_img [L][H*W*3] (and overwrites out_img [L][H*W*3] if given).  spp, sppe and sppse shard ranges are honoured as for kind 4.
+   A render call of this kind without lights is an error.  The caller scales plane l by light l's RGB intensity. */
+#define PSDR_INTEGRATOR_POINT_STACK 5
+#define PSDR_POINT_LIGHTS_MAX 256
 /* FieldExtractionIntegrator fields (src/integrator/field.cpp:10-54) */
 #define PSDR_FIELD_SILHOUETTE 0
 #define PSDR_FIELD_POSITION   1
@@ -381,6 +388,12 @@ int psdr_scene_set_path_guide(psdr_scene_t h, const int32_t reso[3], const float
    psdr_render_d_fwd reads the first K' rows of its own K, missing rows are zero.  g_pos: DEVICE array [3] that psdr_render_d_rev adds the gradient of
    the position into (+=; the caller zeroes it and keeps it alive), or NULL.  pos == NULL removes the light.  The light survives psdr_scene_set_tables. */
 int psdr_scene_set_point_light(psdr_scene_t h, const float pos[3], int32_t K, const float *d_pos, float *g_pos);
+/* The lights of PSDR_INTEGRATOR_POINT_STACK, L = 1 .. PSDR_POINT_LIGHTS_MAX.  pos: HOST array [L][3] of world positions (copied).  d_pos: HOST array
+   [K][L][3] of position tangents (copied; K = 0..3) or NULL -- psdr_render_d_fwd reads the first K' sets of its own K, missing sets are zero.  g_pos: DEVICE
+   array [L][3] that psdr_render_d_rev adds the gradients of the positions into (+=; the caller zeroes it and keeps it alive), or NULL.  pos == NULL or
+   L == 0 removes the lights.  They survive psdr_scene_set_tables and are independent of psdr_scene_set_point_light: PSDR_INTEGRATOR_POINT keeps reading
+   its own light. */
+int psdr_scene_set_point_lights(psdr_scene_t h, int32_t L, const float *pos, int32_t K, const float *d_pos, float *g_pos);
 int psdr_path_guide_build(psdr_scene_t h, const psdr_render_opts *opts, int32_t segment,
                           const int32_t reso[4], int32_t nrounds,
                           float *out_mass, void *stream);

@@ -489,7 +489,7 @@ void fill_top(const psdr_scene_s *h, SceneView &sc) {
 int make_ctx(psdr_scene_s *h, const psdr_render_opts *o, int sampler, LaunchCtx &cx) {
     if (!h->have_tables) return fail("Scene not loaded yet!");
     if (!h->have_bvh) return fail("Input scene must be configured!");
-    if (o->integrator != PSDR_INTEGRATOR_FIELD && o->integrator != PSDR_INTEGRATOR_COLLOCATED && o->integrator != PSDR_INTEGRATOR_POINT && h->desc.num_emitters <= 0) return fail("No Emitter!");
+    if (o->integrator != PSDR_INTEGRATOR_FIELD && o->integrator != PSDR_INTEGRATOR_COLLOCATED && o->integrator != PSDR_INTEGRATOR_POINT && o->integrator != PSDR_INTEGRATOR_POINT_STACK && h->desc.num_emitters <= 0) return fail("No Emitter!");
     if (o->integrator == PSDR_INTEGRATOR_DIRECT && !(o->bsdf_samples >= 0 && o->light_samples >= 0 && o->bsdf_samples + o->light_samples > 0))
         return fail("DirectIntegrator: bsdf_samples + light_samples must be positive");
     cx.sc.d = h->desc; cx.sc.nodes = h->d_nodes; cx.sc.btris = h->d_btris; cx.sc.root = h->root;
@@ -808,9 +808,11 @@ const VariantOps *variant_of(const psdr_scene_s *h) { PSDR_OPS_OF(variant_ops_) 
 const PathSedgeOps *path_sedge_of(const psdr_scene_s *h) { PSDR_OPS_OF(path_sedge_ops_) }
 const CollocatedOps *collocated_of(const psdr_scene_s *h) { PSDR_OPS_OF(collocated_ops_) }
 const PointLightOps *point_light_of(const psdr_scene_s *h) { PSDR_OPS_OF(point_light_ops_) }
+const LightStageOps *light_stage_of(const psdr_scene_s *h) { PSDR_OPS_OF(light_stage_ops_) }
 // PSDR_INTEGRATOR_POINT without a light: an error before any launch
 int check_point_light(const psdr_scene_s *h, const psdr_render_opts *o) {
     if (o->integrator == PSDR_INTEGRATOR_POINT && !h->have_point) return fail("PointLightIntegrator: no light set (psdr_scene_set_point_light)");
+    if (o->integrator == PSDR_INTEGRATOR_POINT_STACK && h->stack_pos.empty()) return fail("LightStageIntegrator: no lights set (psdr_scene_set_point_lights)");
     return 0;
 }
 #undef PSDR_OPS_OF
@@ -892,6 +894,7 @@ int psdr_scene_set_option(psdr_scene_t h, const char *name, double value) {
 int psdr_scene_destroy(psdr_scene_t h) {
     if (!h) return 0;
     if (h->d_nodes) (void) hipFree(h->d_nodes);
+    if (h->d_stack_lights) (void) hipFree(h->d_stack_lights);
     if (h->d_btris) (void) hipFree(h->d_btris);
     if (h->d_counters) (void) hipFree(h->d_counters);
     if (h->d_refit_area) (void) hipFree(h->d_refit_area);
@@ -1207,6 +1210,7 @@ int psdr_render_c(psdr_scene_t h, const psdr_render_opts *o, float *out_img, voi
     if (int rc = begin_call(h, s)) return rc;
     if (o->integrator == PSDR_INTEGRATOR_PATH) h->last_path_depth = o->max_depth;
     const long long WH = (long long) h->desc.width * h->desc.height;
+    if (o->integrator == PSDR_INTEGRATOR_POINT_STACK) return light_stage_of(h)->render_c(h, o, out_img, s);          // out_img [L][W H 3]
     HIP_TRY(hipMemsetAsync(out_img, 0, sizeof(float) * WH * 3, s));
     if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_c(h, o, out_img, s);
     if (o->integrator == PSDR_INTEGRATOR_POINT) return point_light_of(h)->render_c(h, o, out_img, s);
@@ -1224,6 +1228,7 @@ int psdr_render_d_fwd(psdr_scene_t h, const psdr_render_opts *o, int32_t K, cons
     hipStream_t s = (hipStream_t) stream;
     if (int rc = begin_call(h, s)) return rc;
     if (K != 1 && K != 3) return fail("psdr_render_d_fwd: K must be 1 or 3");
+    if (o->integrator == PSDR_INTEGRATOR_POINT_STACK) return light_stage_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, point_light_of(h), s);          // [L] and [K][L] planes
     if (o->integrator == PSDR_INTEGRATOR_POINT) return point_light_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s);          // interior + primary edges + shadow boundary
     if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s);          // interior + primary edges: no secondary-edge term
     if (int rc = variant_of(h)->render_fwd(h, o, K, tangents, out_img, out_dimg, s)) return rc;
@@ -1246,6 +1251,7 @@ int psdr_render_d_rev(psdr_scene_t h, const psdr_render_opts *o, const float *ad
     std::fill(std::begin(h->rev_layout), std::end(h->rev_layout), 0);
     h->rev_layout[8] = -1;                                                // (no camera launch)
     if (o->integrator == PSDR_INTEGRATOR_COLLOCATED) return collocated_of(h)->render_rev(h, o, adj_img, out_img, grads, s);
+    if (o->integrator == PSDR_INTEGRATOR_POINT_STACK) return light_stage_of(h)->render_rev(h, o, adj_img, out_img, grads, point_light_of(h), s);
     if (o->integrator == PSDR_INTEGRATOR_POINT) return point_light_of(h)->render_rev(h, o, adj_img, out_img, grads, s);
     if (int rc = variant_of(h)->render_rev(h, o, adj_img, out_img, grads, s)) return rc;
     return path_sedge_of(h)->rev(h, o, adj_img, grads, s);                 // PSDR_FLAG_PATH_SEDGES (nothing without it)
@@ -1262,6 +1268,24 @@ int psdr_scene_set_point_light(psdr_scene_t h, const float pos[3], int32_t K, co
     for (int c = 0; c < 3; ++c) h->point_pos[c] = pos[c];
     if (d_pos != nullptr) { h->point_K = K; std::memcpy(h->point_dpos, d_pos, sizeof(float) * 3 * (size_t) K); }
     h->point_gpos = g_pos;
+    return 0;
+}
+
+int psdr_scene_set_point_lights(psdr_scene_t h, int32_t L, const float *pos, int32_t K, const float *d_pos, float *g_pos) {
+    if (!h) return fail("psdr_scene_set_point_lights: null handle");
+    if (pos != nullptr && L != 0) {
+        if (L < 1 || L > PSDR_POINT_LIGHTS_MAX) return fail("psdr_scene_set_point_lights: L must be 1.." + std::to_string(PSDR_POINT_LIGHTS_MAX));
+        if (K < 0 || K > 3) return fail("psdr_scene_set_point_lights: K must be 0..3");
+        for (int i = 0; i < 3 * L; ++i) if (!std::isfinite(pos[i])) return fail("psdr_scene_set_point_lights: the position of light " + std::to_string(i / 3) + " is not finite");
+    }
+    h->stack_pos.clear(); h->stack_dpos.clear();
+    h->stack_K = 0; h->stack_gpos = nullptr;
+    if (pos == nullptr || L == 0) return 0;
+    // positions and up to three tangent sets of them
+    if (int rc = device_grow(h->d_stack_lights, h->cap_stack_lights, (size_t) L, sizeof(float) * 12)) return rc;
+    h->stack_pos.assign(pos, pos + 3 * (size_t) L);
+    if (d_pos != nullptr && K > 0) { h->stack_K = K; h->stack_dpos.assign(d_pos, d_pos + 3 * (size_t) L * K); }
+    h->stack_gpos = g_pos;
     return 0;
 }
 

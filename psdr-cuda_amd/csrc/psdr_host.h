@@ -311,6 +311,14 @@ struct psdr_scene_s {
     float point_pos[3] = {0.f, 0.f, 0.f}, point_dpos[3][3] = {};
     int point_K = 0;
     float *point_gpos = nullptr;
+    // the lights of PSDR_INTEGRATOR_POINT_STACK (psdr_scene_set_point_lights), independent of the light above: host copies of the positions [L][3] and of
+    // the K tangents of them [K][L][3], the caller's device gradient [L][3], and the device table the kernels read (positions, then tangents; written on
+    // the call's stream before the launch)
+    std::vector<float> stack_pos, stack_dpos;
+    int stack_K = 0;
+    float *stack_gpos = nullptr;
+    float *d_stack_lights = nullptr;
+    size_t cap_stack_lights = 0;           // in lights
 };
 
 constexpr int kRayCounters = 64, kRayCounterStride = 16;     // d_counters: 64 counters, 128 bytes apart
@@ -394,6 +402,9 @@ struct PointLightOps {
     int (*render_c)(psdr_scene_s *h, const psdr_render_opts *o, float *img, hipStream_t s);
     int (*render_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s);
     int (*render_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, hipStream_t s);
+    // the primary-edge and shadow-boundary terms alone, for a light given by value (the LightStageIntegrator launches them once per light of its stack)
+    int (*edges_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, const float *pos, const float *d_pos, float *dimg, long long plane, hipStream_t s);
+    int (*edges_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, const float *pos, float *g_pos, hipStream_t s);
 };
 const PointLightOps *point_light_ops_0();
 const PointLightOps *point_light_ops_1();
@@ -403,6 +414,22 @@ const PointLightOps *point_light_ops_4();
 const PointLightOps *point_light_ops_6();
 const PointLightOps *point_light_ops_8();
 const PointLightOps *point_light_ops_10();
+// The LightStageIntegrator (PSDR_INTEGRATOR_POINT_STACK, psdr_lightstage.h) per flag set: psdr_lightstage.hip, one more translation unit per set.  Its camera
+// kernels render every light of the handle's stack from one hit per slot; `point`: the PointLightIntegrator's ops of the same flag set, whose edge kernels
+// it launches once per light.
+struct LightStageOps {
+    int (*render_c)(psdr_scene_s *h, const psdr_render_opts *o, float *img, hipStream_t s);
+    int (*render_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, const PointLightOps *point, hipStream_t s);
+    int (*render_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, const PointLightOps *point, hipStream_t s);
+};
+const LightStageOps *light_stage_ops_0();
+const LightStageOps *light_stage_ops_1();
+const LightStageOps *light_stage_ops_2();
+const LightStageOps *light_stage_ops_3();
+const LightStageOps *light_stage_ops_4();
+const LightStageOps *light_stage_ops_6();
+const LightStageOps *light_stage_ops_8();
+const LightStageOps *light_stage_ops_10();
 // The lean twin of the K = 1 log-derivative camera kernel for flag set 8 (psdr_logd_lean.hip): launches it behind the gate kernels of run_camera and
 // sets *ran, or leaves *ran false -- option logd_park 0, or the parking columns do not fit six workgroups per CU (or a forced lds_budget) -- and
 // run_camera launches k_camera_logd.  cx: the launch context of run_camera (off_park is set on a copy).

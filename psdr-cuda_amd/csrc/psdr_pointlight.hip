@@ -288,6 +288,26 @@ int point_render_c(psdr_scene_s *h, const psdr_render_opts *o, float *out_img, h
     return point_run_camera<float, float, FL>(h, o, tv0, light_of(h, 0), out_img, nullptr, s);
 }
 
+// The two edge terms of forward mode for one light: primary edges and the shadow boundary, added into dimg (K planes, `plane` floats apart)
+template <int K, int FL>
+int point_edges_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const TangentView<K, FL> &tv, const PointLight &pl, float *dimg, long long plane, hipStream_t s) {
+    if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0) {
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_edge<K, FL>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppe, dimg, plane,
+                           h->d_counters, e.order);
+        HIP_TRY(hipGetLastError());
+    }
+    if (o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0) {
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_sedge<K, FL>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppse, dimg, plane,
+                           h->d_counters);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 template <int K, int FL>
 int point_render_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s) {
     const long long WH = (long long) h->desc.width * h->desc.height;
@@ -298,21 +318,7 @@ int point_render_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_ta
     HIP_TRY(hipMemsetAsync(dimg, 0, sizeof(float) * WH * 3 * K, s));
     if (tangents_move_geometry(tangents, K) || light_moves(h, K)) { if (int rc = point_run_camera<Dual<K>, Dual<K>, FL>(h, o, tv, pl, img, dimg, s)) return rc; }
     else { if (int rc = point_run_camera<float, Dual<K>, FL>(h, o, tv, pl, img, dimg, s)) return rc; }
-    if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0) {
-        EdgeLaunch e;
-        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_edge<K, FL>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppe, dimg, WH * 3,
-                           h->d_counters, e.order);
-        HIP_TRY(hipGetLastError());
-    }
-    if (o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0) {
-        EdgeLaunch e;
-        if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_sedge<K, FL>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppse, dimg, WH * 3,
-                           h->d_counters);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return point_edges_fwd_k<K, FL>(h, o, tv, pl, dimg, WH * 3, s);
 }
 template <int FL>
 int point_render_fwd(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s) {
@@ -321,6 +327,31 @@ int point_render_fwd(psdr_scene_s *h, const psdr_render_opts *o, int K, const ps
         case 3: return point_render_fwd_k<3, FL>(h, o, tangents, img, dimg, s);
         default: return fail("psdr_render_d_fwd: K must be 1 or 3");
     }
+}
+
+// The two edge terms of reverse mode for one light (gradient of its position: g_pos, +=, or null)
+template <int FL>
+int point_edges_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, DeviceSink<FL> &sink, const PointLight &pl, float *g_pos, hipStream_t s) {
+    if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0 && grads->g_prim_edge) {
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
+        PrimaryEdgeSink<FL> pe_sink;
+        if (int rc = begin_pe_replicas(h, grads, e, pe_sink, s)) return rc;
+        hipLaunchKernelGGL(k_point_edge_rev<FL>, dim3(launch_blocks(h, e.n, big_launch_per_cu(h, e.n))), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, pe_sink, pl, e.i0, e.n, 1.f / (float) o->sppe,
+                           adj_img, h->d_counters, e.order);
+        HIP_TRY(hipGetLastError());
+        if (int rc = end_pe_replicas(h, grads, pe_sink, s)) return rc;
+    }
+    if (o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0 && (grads->g_sec_edge != nullptr || grads->g_tri_info != nullptr || g_pos != nullptr)) {
+        EdgeLaunch e;
+        if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
+        int dyn_bytes = 0;
+        if (int rc = plan_rev_one_vertex(h, e.cx, sink.L, &dyn_bytes)) return rc;
+        if (int rc = allow_dynamic_lds(&k_point_sedge_rev<FL>, dyn_bytes)) return rc;
+        hipLaunchKernelGGL(k_point_sedge_rev<FL>, dim3(launch_blocks(h, e.n)), dim3(kBlock), dyn_bytes, s, e.cx, sink, pl, g_pos, e.i0, e.n, 1.f / (float) o->sppse, adj_img, h->d_counters);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
 }
 
 template <int FL>
@@ -350,33 +381,35 @@ int point_render_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *ad
 #undef PSDR_LAUNCH_POINT_REV
         HIP_TRY(hipGetLastError());
     }
-    if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0 && grads->g_prim_edge) {
-        EdgeLaunch e;
-        if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
-        PrimaryEdgeSink<FL> pe_sink;
-        if (int rc = begin_pe_replicas(h, grads, e, pe_sink, s)) return rc;
-        hipLaunchKernelGGL(k_point_edge_rev<FL>, dim3(launch_blocks(h, e.n, big_launch_per_cu(h, e.n))), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, pe_sink, pl, e.i0, e.n, 1.f / (float) o->sppe,
-                           adj_img, h->d_counters, e.order);
-        HIP_TRY(hipGetLastError());
-        if (int rc = end_pe_replicas(h, grads, pe_sink, s)) return rc;
-    }
-    if (o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0 && (grads->g_sec_edge != nullptr || grads->g_tri_info != nullptr || g_pos != nullptr)) {
-        EdgeLaunch e;
-        if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
-        int dyn_bytes = 0;
-        if (int rc = plan_rev_one_vertex(h, e.cx, sink.L, &dyn_bytes)) return rc;
-        if (int rc = allow_dynamic_lds(&k_point_sedge_rev<FL>, dyn_bytes)) return rc;
-        hipLaunchKernelGGL(k_point_sedge_rev<FL>, dim3(launch_blocks(h, e.n)), dim3(kBlock), dyn_bytes, s, e.cx, sink, pl, g_pos, e.i0, e.n, 1.f / (float) o->sppse, adj_img, h->d_counters);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return point_edges_rev<FL>(h, o, adj_img, grads, sink, pl, g_pos, s);
+}
+
+// The edge terms for a light given by value, as the LightStageIntegrator (psdr_lightstage.hip) launches them once per light of its stack:
+// pos [3], d_pos [K][3] or null; dimg: the light's first derivative plane, `plane` floats to the next tangent's
+template <int FL>
+int point_edges_fwd_of(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, const float *pos, const float *d_pos, float *dimg, long long plane, hipStream_t s) {
+    PointLight pl{};
+    for (int c = 0; c < 3; ++c) pl.p[c] = pos[c];
+    for (int k = 0; k < K && d_pos; ++k) for (int c = 0; c < 3; ++c) pl.d[k][c] = d_pos[3 * k + c];
+    if (K == 1) { TangentView<1, FL> tv; tv.t[0] = tangents[0]; return point_edges_fwd_k<1, FL>(h, o, tv, pl, dimg, plane, s); }
+    TangentView<3, FL> tv;
+    for (int k = 0; k < 3; ++k) tv.t[k] = tangents[k];
+    return point_edges_fwd_k<3, FL>(h, o, tv, pl, dimg, plane, s);
+}
+template <int FL>
+int point_edges_rev_of(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, const float *pos, float *g_pos, hipStream_t s) {
+    PointLight pl{};
+    for (int c = 0; c < 3; ++c) pl.p[c] = pos[c];
+    DeviceSink<FL> sink{};
+    if (int rc = make_device_sink(h, grads, sink)) return rc;
+    return point_edges_rev<FL>(h, o, adj_img, grads, sink, pl, g_pos, s);
 }
 }  // namespace
 
 namespace psdr_host {
 const PointLightOps *PSDR_CAT(point_light_ops_, PSDR_VARIANT_FLAGS)() {
     constexpr int FL = PSDR_VARIANT_FLAGS;
-    static const PointLightOps ops{&point_render_c<FL>, &point_render_fwd<FL>, &point_render_rev<FL>};
+    static const PointLightOps ops{&point_render_c<FL>, &point_render_fwd<FL>, &point_render_rev<FL>, &point_edges_fwd_of<FL>, &point_edges_rev_of<FL>};
     return &ops;
 }
 }  // namespace psdr_host

@@ -240,6 +240,10 @@ class Integrator(Object):
             scene._rng_offset[2] += d[2]
 
     # ---- native plumbing ----------------------------------------------------------
+    def _image_floats(self, tb):
+        """floats of one image of this integrator (the LightStageIntegrator renders one plane per light)"""
+        return tb["width"] * tb["height"] * 3
+
     def _prepare(self, scene, tb, guide):
         lib = _abi.load_hip()
         if not torch.cuda.is_available():
@@ -266,7 +270,7 @@ class Integrator(Object):
         if keep_records and self._kind == _abi.INTEGRATOR_PATH:
             opts = type(opts).from_buffer_copy(opts)
             opts.flags |= _abi.FLAG_KEEP_RECORDS
-        img = torch.empty(tb["width"] * tb["height"] * 3, dtype=torch.float32, device="cuda")
+        img = torch.empty(self._image_floats(tb), dtype=torch.float32, device="cuda")
         _abi.check(lib, lib.psdr_render_c(scene._native, C.byref(opts), img.data_ptr(), _stream_ptr()))
         self._counters(lib, scene)
         dist = _dist()
@@ -279,7 +283,7 @@ class Integrator(Object):
     def _render_fwd(self, scene, tb, opts, guide, tangent_sets):
         lib, keep = self._prepare(scene, tb, guide)
         K = len(tangent_sets)
-        n = tb["width"] * tb["height"] * 3
+        n = self._image_floats(tb)
         buf = torch.empty((1 + K) * n, dtype=torch.float32, device="cuda")   # [image || derivative images]: one all-reduce
         tarr = (_abi.Tangents * K)()
         for k, ts in enumerate(tangent_sets):
@@ -759,6 +763,172 @@ class PointLightIntegrator(CollocatedIntegrator):
         if not (tb.get("num_sec_edges", 0) > 0):
             opts.sppse = opts.sppse_begin = opts.sppse_end = 0
         img = _CollocatedImage._make(_PointLightNode(_RenderNode(self, scene, sensor_id, tb, opts, None), self.m_intensity, self.m_position))
+        self._advance_rng(scene, opts)
+        ek.register_render_node(img)
+        if scene.opts.log_level:
+            img.t                                        # (the log line reports the render's time)
+            torch.cuda.synchronize()
+            self.log("Rendered in %g seconds." % (time.perf_counter() - t0))
+        return img
+
+
+class _StackRenderFn(torch.autograd.Function):
+    """torch.autograd bridge of the LightStageIntegrator's reverse mode: _PointRenderFn with the positions of all lights as the extra input; their
+    gradients come back in a device array [L, 3]."""
+
+    @staticmethod
+    def forward(ctx, node, pos, *inputs):
+        ctx.node, ctx.present, ctx.pos_shape = node, [t is not None for t in inputs], pos.shape
+        unit = node.unit
+        with _decided(unit.collective), unit.integrator._lights(node.pos):
+            img = unit.integrator._render_c(unit.scene, unit.tb, unit.opts, unit.guide, interior_only=True)
+        return img.reshape(-1, 3)
+
+    @staticmethod
+    def backward(ctx, adj):
+        node, unit = ctx.node, ctx.node.unit
+        g_pos = torch.zeros((len(node.pos), 3), dtype=torch.float32, device="cuda") if ctx.needs_input_grad[1] else None
+        with _decided(unit.collective), unit.integrator._lights(node.pos, g_pos=g_pos):
+            grads = unit.integrator._render_rev(unit.scene, unit.tb, unit.opts, unit.guide, adj.contiguous().reshape(-1))
+            dist = _dist()
+            if dist and g_pos is not None:
+                dist.all_reduce(g_pos)
+            unit.integrator._forget_lights(unit.scene)          # the handle must not keep the address of g_pos beyond this call
+        out = [None, g_pos.reshape(ctx.pos_shape) if g_pos is not None else None]
+        for k, present in zip(_AD_KEYS, ctx.present):
+            out.append(grads.get(k) if present else None)
+        return tuple(out)
+
+
+class _LightStageNode:
+    """renderD of the LightStageIntegrator: the unit-intensity render node of the whole stack ([L W H, 3], light-major), the intensities [L, 3] that scale
+    plane l on the host and the positions [L, 3] (their values at the renderD call are the ones every deferred launch of the node uses).  enoki.forward
+    sees nine inputs: the seven tables, the intensities and the positions.  combine: the image is sum_l intensity_l * unit_l, formed in torch."""
+
+    def __init__(self, unit, intensities, positions, combine):
+        self.unit, self.intensities, self.positions, self.combine = unit, intensities, positions, combine
+        self.pos = [[float(x) for x in row] for row in positions.t.detach().reshape(-1, 3).cpu()]
+
+    def input_tensors(self):
+        return self.unit.input_tensors() + [self.intensities.t, self.positions.t]
+
+    def _assemble(self, planes, scale):
+        """planes [L W H, 3] x scale [L, 3] -> the stack [L W H, 3] or, combined, its sum over the lights [W H, 3]"""
+        L = len(self.pos)
+        stack = planes.reshape(L, -1, 3) * scale.reshape(L, 1, 3).to(planes.device)
+        return stack.sum(dim=0) if self.combine else stack.reshape(-1, 3)
+
+    def render_forward(self, tangents):
+        d_int, d_pos = tangents[-2], tangents[-1]
+        dp = None if d_pos is None else [[float(x) for x in row] for row in d_pos.detach().reshape(-1, 3).cpu()]
+        with self.unit.integrator._lights(self.pos, d_pos=dp):
+            d_unit = self.unit.render_forward(list(tangents[:-2]))          # one forward-mode launch: the unit stack and its derivative
+        unit, scale = self.unit.primal, self.intensities.t.detach()
+        self.primal = self._assemble(unit, scale)
+        d = self._assemble(d_unit, scale)
+        if d_int is not None:
+            d = d + self._assemble(unit, d_int.detach())
+        return d
+
+    def render_primal(self):
+        unit, inputs = self.unit, self.unit.input_tensors()
+        with torch.enable_grad():
+            pos = self.positions.t
+            if pos.requires_grad or any(t is not None and t.requires_grad for t in inputs):
+                img = _StackRenderFn.apply(self, pos, *inputs)
+            else:
+                with _decided(unit.collective), unit.integrator._lights(self.pos):
+                    img = unit.integrator._render_c(unit.scene, unit.tb, unit.opts, unit.guide, interior_only=True).reshape(-1, 3)
+            return self._assemble(img, self.intensities.t)
+
+    def release(self):
+        pass
+
+
+class LightStageIntegrator(PointLightIntegrator):
+    """L point lights rendered and differentiated in ONE call: the set-up of photometric stereo (3 to 12 lamps) and of a light stage (dozens).  NOT in the
+    reference snapshot: build-defined.  Plane l is the PointLightIntegrator's image under light l -- the kernels (csrc/psdr_lightstage.h) find one hit per
+    camera sample and loop over the lights from it, so the film jitter, the primary ray, the walk, the hit and, in reverse mode, the hit's adjoint chain
+    are shared; the edge terms run per light.
+
+    positions: an [L, 3] array (1 <= L <= 256) or a Vector3fD of L rows, kept as the differentiable attribute m_positions; intensities: a float, one RGB
+    triple or [L, 3] (or a Vector3fD of L rows), kept as m_intensities.  combine=False: renderC / renderD return L*H*W rows, light-major, plane l scaled
+    by intensity l.  combine=True: they return the one image sum_l intensity_l * unit_l (H*W rows), formed in torch from the stack.  The tables, the
+    intensities and the positions take part in enoki.forward and enoki.backward."""
+    _type_name = "LightStageIntegrator"
+    _kind = _abi.INTEGRATOR_POINT_STACK
+
+    def __init__(self, positions, intensities=1.0, combine=False):
+        Integrator.__init__(self)
+        if isinstance(positions, Vector3fD):
+            psdr_assert(positions.t.dim() == 2 and positions.t.shape[1] == 3, "positions: [L, 3] expected")
+            self.m_positions = positions
+        else:
+            p = np.asarray(positions, dtype=np.float64)
+            psdr_assert(p.ndim == 2 and p.shape[1] == 3 and np.isfinite(p).all(), "positions: an [L, 3] array of finite floats expected")
+            self.m_positions = Vector3fD(torch.from_numpy(p.astype(np.float32)))
+        L = int(self.m_positions.t.shape[0])
+        psdr_assert(1 <= L <= _abi.POINT_LIGHTS_MAX, "positions: between 1 and %d lights expected" % _abi.POINT_LIGHTS_MAX)
+        if isinstance(intensities, Vector3fD):
+            psdr_assert(tuple(intensities.t.shape) == (L, 3), "intensities: [L, 3] expected")
+            self.m_intensities = intensities
+        else:
+            v = np.asarray(intensities, dtype=np.float64)
+            psdr_assert(v.size in (1, 3) or v.shape == (L, 3), "intensities: a float, three floats or [L, 3] expected")
+            v = np.broadcast_to(v.reshape(1, -1) if v.size in (1, 3) else v, (L, 3))
+            self.m_intensities = Vector3fD(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)))
+        self.combine = bool(combine)
+        self._light_state = None
+
+    def _lights(self, pos, d_pos=None, g_pos=None):
+        """the lights every native call inside the block renders with (positions [L][3], their tangents in forward mode, their device gradient in reverse mode)"""
+        return _light_scope(self, pos, d_pos, g_pos)
+
+    def _image_floats(self, tb):
+        return len(self._light_state[0]) * tb["width"] * tb["height"] * 3
+
+    def _prepare(self, scene, tb, guide):
+        lib, keep = Integrator._prepare(self, scene, tb, guide)
+        psdr_assert(self._light_state is not None, "LightStageIntegrator: no lights in scope")
+        pos, d_pos, g_pos = self._light_state
+        L = len(pos)
+        flat = [x for row in pos for x in row]
+        dflat = None if d_pos is None else [x for row in d_pos for x in row]
+        _abi.check(lib, lib.psdr_scene_set_point_lights(scene._native, L, (C.c_float * (3 * L))(*flat), 0 if d_pos is None else 1,
+                                                        None if d_pos is None else (C.c_float * (3 * L))(*dflat), None if g_pos is None else g_pos.data_ptr()))
+        if g_pos is not None:
+            keep.append(g_pos)
+        return lib, keep
+
+    def _forget_lights(self, scene):
+        """removes the lights from the scene's handle (with them the tangents and the gradient address of the last call); the next native call sets its own"""
+        if scene._native is not None:
+            lib = _abi.load_hip()
+            _abi.check(lib, lib.psdr_scene_set_point_lights(scene._native, 0, None, 0, None, None))
+
+    def _positions_now(self):
+        return [[float(x) for x in row] for row in self.m_positions.t.detach().reshape(-1, 3).cpu()]
+
+    def renderC(self, scene, sensor_id=0):
+        pos = self._positions_now()
+        with self._lights(pos):
+            img = Integrator.renderC(self, scene, sensor_id)          # unit intensities, [L W H, 3] (joins the image's all-reduce)
+        L = len(pos)
+        stack = img.t.reshape(L, -1, 3) * self.m_intensities.t.detach().reshape(L, 1, 3).to(img.t.device)
+        return Vector3fC._wrap(stack.sum(dim=0) if self.combine else stack.reshape(-1, 3))
+
+    def renderD(self, scene, sensor_id=0):
+        self._check_bsdfs(scene)
+        psdr_assert(scene.is_ready(), "Input scene must be configured!")
+        psdr_assert(0 <= sensor_id < scene.num_sensors, "Invalid sensor id!")
+        t0 = time.perf_counter()
+        tb = scene.tables(sensor_id, capacity=True)
+        opts = self._opts(scene, with_edges=True)
+        if not (scene._sensor_tables[sensor_id]["num_prim_edges"] > 0):
+            opts.sppe = opts.sppe_begin = opts.sppe_end = 0
+        if not (tb.get("num_sec_edges", 0) > 0):
+            opts.sppse = opts.sppse_begin = opts.sppse_end = 0
+        img = _CollocatedImage._make(_LightStageNode(_RenderNode(self, scene, sensor_id, tb, opts, None), self.m_intensities, self.m_positions, self.combine))
         self._advance_rng(scene, opts)
         ek.register_render_node(img)
         if scene.opts.log_level:
