@@ -8,6 +8,7 @@
     python examples/inverse_rendering.py svbrdf --normals     # ... of a quad with a bumpy normal map: albedo, roughness and normals
     python examples/inverse_rendering.py svbrdf --normals --lights     # ... from ONE view under three lamps (PointLightIntegrator), beside the three-tilt run
     python examples/inverse_rendering.py svbrdf --normals --lights --stack     # ... and with the three lamps as one LightStageIntegrator: ms per step of both
+    python examples/inverse_rendering.py svbrdf --normals --lights --distant   # ... and with the three lamps as distant lights (DistantLightIntegrator)
     python examples/inverse_rendering.py svbrdf --height      # ... of a quad with a relief: albedo, roughness and a height map
     python examples/inverse_rendering.py shape        # recover a displaced sphere's vertices, one by one, through psdr_cuda.LargeSteps
 
@@ -106,7 +107,7 @@ SVBRDF_XML = """<scene version="0.5.0">
 </scene>"""
 
 
-def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False, height=False, lights=False, stack=False):
+def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normals=False, height=False, lights=False, stack=False, distant=False):
     """A quad with map_res x map_res kd and roughness maps (MicrofacetBSDF, F0 known) photographed with a flash at the camera under three tilts -- one quad
     transformed three times, the maps shared.  The diffuse lobe is seen at every tilt, the specular lobe only near normal incidence, so the two maps separate by
     angle.  Adam on both maps from a flat start; the flash's intensity brings the pixel values (1 / distance^2 = 1e-6) to order 0.1.
@@ -118,7 +119,9 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
     lights (--normals --lights): ONE camera, the quad head-on, and three lamps 120 degrees apart around the viewing axis, about 37 degrees off it
     (PointLightIntegrator, one per lamp: photometric stereo) instead of three tilts under the flash.
     stack (--normals --lights --stack): the three lamps as ONE LightStageIntegrator -- one renderD and one backward per step, the three photographs are the planes
-    of its image.  Returns the final mean angular error of the normals, if any (with lights: that and the ms per step)."""
+    of its image.
+    distant (--normals --lights --distant): the three lamps as DISTANT lights (DistantLightIntegrator): their directions are the lamps' seen from the quad's centre,
+    their irradiance what the lamps give there (1e6 / 1000^2 = 1) -- the light model of calibrated photometric stereo.  Returns the final mean angular error of the normals, if any (with lights: that and the ms per step)."""
     rng = np.random.default_rng(3)
     kd_true = rng.uniform(0.2, 0.8, (map_res * map_res, 3)).astype(np.float32)
     r_true = rng.uniform(0.3, 0.6, map_res * map_res).astype(np.float32)
@@ -135,6 +138,8 @@ def svbrdf(map_res=16, res=64, spp=8, steps=150, tilts=(0.0, 35.0, 65.0), normal
             tilts = ((0.0, 0.0),) * 3
             lamps = [(600.0 * np.cos(a), 125.0 + 600.0 * np.sin(a), 800.0) for a in np.radians([0.0, 120.0, 240.0])]
             integs = [psdr_cuda.PointLightIntegrator(p, 1e6) for p in lamps]
+            if distant:
+                integs = [psdr_cuda.DistantLightIntegrator((p[0], p[1] - 125.0, p[2]), 1.0) for p in lamps]
             if stack:
                 tilts, integs = ((0.0, 0.0),), [psdr_cuda.LightStageIntegrator(lamps, 1e6)]
 
@@ -283,6 +288,10 @@ if __name__ == "__main__":
         print("one view under three lamps (PointLightIntegrator):")
         lit, lit_ms = svbrdf(normals=True, lights=True)
         print("mean angular error of the normals: three lamps %.2f degrees, three tilts %.2f degrees" % (lit, tilted))
+        if "--distant" in sys.argv[2:]:
+            print("one view under three distant lamps (DistantLightIntegrator):")
+            far, far_ms = svbrdf(normals=True, lights=True, distant=True)
+            print("mean angular error of the normals: three distant lamps %.2f degrees (%.1f ms per step), three point lamps %.2f degrees (%.1f ms per step)" % (far, far_ms, lit, lit_ms))
         if "--stack" in sys.argv[2:]:
             print("one view under three lamps as one stack (LightStageIntegrator):")
             stacked, stacked_ms = svbrdf(normals=True, lights=True, stack=True)

@@ -132,6 +132,15 @@ extern "C" {
    A render call of this kind without lights is an error.  The caller scales plane l by light l's RGB intensity. */
 #define PSDR_INTEGRATOR_POINT_STACK 5
 #define PSDR_POINT_LIGHTS_MAX 256
+/* The light models of kinds 4 and 5 (psdr_scene_set_light / psdr_scene_set_lights).  PSDR_LIGHT_POINT: the text above.  PSDR_LIGHT_DISTANT: the light's
+   vector is a DIRECTION d that points from the scene TOWARDS the light, of any non-zero length; with u = d / |d|
+       Li = f(its; wi = its.wi, wo = to_local(u)) * V(its.p, u),   V = 0 if the ray (its.p, u) meets a surface at any t >= RayEpsilon.
+   No 1 / r^2: the unit light gives unit IRRADIANCE to a surface that faces it (the caller scales by the irradiance, RGB), so a point light at c + R u
+   with intensity R^2 tends to this model.  The gradient of the light is that of d as passed: it has no component along d and scales as 1 / |d|.
+   The shadow-boundary term is that of the parallel projection along -u.  A distant light cannot reach a scene inside an environment map's bounding
+   mesh: a render call of kind 4 or 5 with a distant light on such a scene is an error. */
+#define PSDR_LIGHT_POINT   0
+#define PSDR_LIGHT_DISTANT 1
 /* FieldExtractionIntegrator fields (src/integrator/field.cpp:10-54) */
 #define PSDR_FIELD_SILHOUETTE 0
 #define PSDR_FIELD_POSITION   1
@@ -394,6 +403,12 @@ int psdr_scene_set_point_light(psdr_scene_t h, const float pos[3], int32_t K, co
    L == 0 removes the lights.  They survive psdr_scene_set_tables and are independent of psdr_scene_set_point_light: PSDR_INTEGRATOR_POINT keeps reading
    its own light. */
 int psdr_scene_set_point_lights(psdr_scene_t h, int32_t L, const float *pos, int32_t K, const float *d_pos, float *g_pos);
+/* The same two with a light model per light (PSDR_LIGHT_POINT / PSDR_LIGHT_DISTANT); the two above mean PSDR_LIGHT_POINT.  v: the position, or the
+   direction TOWARDS the light (any non-zero, finite length); d_v: its tangents; g_v: the gradient of that vector as passed -- for a direction it is
+   tangential (no component along d) and scales as 1 / |d|.  kinds: HOST array [L] (copied); a stack may mix the kinds in any order.  Errors: an unknown
+   kind, a vector that is not finite, a direction that is all zero.  v == NULL (or L == 0) removes the light(s). */
+int psdr_scene_set_light(psdr_scene_t h, int32_t kind, const float v[3], int32_t K, const float *d_v, float *g_v);
+int psdr_scene_set_lights(psdr_scene_t h, int32_t L, const int32_t *kinds, const float *v, int32_t K, const float *d_v, float *g_v);
 int psdr_path_guide_build(psdr_scene_t h, const psdr_render_opts *opts, int32_t segment,
                           const int32_t reso[4], int32_t nrounds,
                           float *out_mass, void *stream);

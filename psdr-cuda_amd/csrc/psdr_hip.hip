@@ -809,10 +809,17 @@ const PathSedgeOps *path_sedge_of(const psdr_scene_s *h) { PSDR_OPS_OF(path_sedg
 const CollocatedOps *collocated_of(const psdr_scene_s *h) { PSDR_OPS_OF(collocated_ops_) }
 const PointLightOps *point_light_of(const psdr_scene_s *h) { PSDR_OPS_OF(point_light_ops_) }
 const LightStageOps *light_stage_of(const psdr_scene_s *h) { PSDR_OPS_OF(light_stage_ops_) }
-// PSDR_INTEGRATOR_POINT without a light: an error before any launch
+// PSDR_INTEGRATOR_POINT without a light: an error before any launch.  So is a distant light under an environment map: the map's bounding mesh occludes
+// like any surface, and the light is outside it by definition.
+const char *const kDistantInEnv = "a distant light cannot reach a scene inside an environment map's bounding mesh (env_emitter >= 0)";
 int check_point_light(const psdr_scene_s *h, const psdr_render_opts *o) {
     if (o->integrator == PSDR_INTEGRATOR_POINT && !h->have_point) return fail("PointLightIntegrator: no light set (psdr_scene_set_point_light)");
     if (o->integrator == PSDR_INTEGRATOR_POINT_STACK && h->stack_pos.empty()) return fail("LightStageIntegrator: no lights set (psdr_scene_set_point_lights)");
+    if (h->desc.env_emitter >= 0) {
+        const bool distant = o->integrator == PSDR_INTEGRATOR_POINT ? h->point_kind == PSDR_LIGHT_DISTANT
+                           : o->integrator == PSDR_INTEGRATOR_POINT_STACK && std::find(h->stack_kind.begin(), h->stack_kind.end(), PSDR_LIGHT_DISTANT) != h->stack_kind.end();
+        if (distant) return fail(kDistantInEnv);
+    }
     return 0;
 }
 #undef PSDR_OPS_OF
@@ -1262,6 +1269,7 @@ int psdr_scene_set_point_light(psdr_scene_t h, const float pos[3], int32_t K, co
     if (K < 0 || K > 3) return fail("psdr_scene_set_point_light: K must be 0..3");
     if (pos != nullptr && !(std::isfinite(pos[0]) && std::isfinite(pos[1]) && std::isfinite(pos[2]))) return fail("psdr_scene_set_point_light: the position is not finite");
     h->have_point = pos != nullptr;
+    h->point_kind = PSDR_LIGHT_POINT;          // (psdr_scene_set_light sets its kind after this call)
     h->point_K = 0; h->point_gpos = nullptr;
     std::memset(h->point_dpos, 0, sizeof(h->point_dpos));
     if (pos == nullptr) return 0;
@@ -1278,14 +1286,44 @@ int psdr_scene_set_point_lights(psdr_scene_t h, int32_t L, const float *pos, int
         if (K < 0 || K > 3) return fail("psdr_scene_set_point_lights: K must be 0..3");
         for (int i = 0; i < 3 * L; ++i) if (!std::isfinite(pos[i])) return fail("psdr_scene_set_point_lights: the position of light " + std::to_string(i / 3) + " is not finite");
     }
-    h->stack_pos.clear(); h->stack_dpos.clear();
+    h->stack_pos.clear(); h->stack_dpos.clear(); h->stack_kind.clear();
     h->stack_K = 0; h->stack_gpos = nullptr;
     if (pos == nullptr || L == 0) return 0;
-    // positions and up to three tangent sets of them
-    if (int rc = device_grow(h->d_stack_lights, h->cap_stack_lights, (size_t) L, sizeof(float) * 12)) return rc;
+    // positions, up to three tangent sets of them and the kinds
+    if (int rc = device_grow(h->d_stack_lights, h->cap_stack_lights, (size_t) L, sizeof(float) * 13)) return rc;
     h->stack_pos.assign(pos, pos + 3 * (size_t) L);
+    h->stack_kind.assign((size_t) L, PSDR_LIGHT_POINT);
     if (d_pos != nullptr && K > 0) { h->stack_K = K; h->stack_dpos.assign(d_pos, d_pos + 3 * (size_t) L * K); }
     h->stack_gpos = g_pos;
+    return 0;
+}
+
+// the checks the kinds add to the two entry points above, which do the rest
+static int check_light_vector(const char *fn, int kind, const float *v, const std::string &which) {
+    if (kind != PSDR_LIGHT_POINT && kind != PSDR_LIGHT_DISTANT) return fail(std::string(fn) + ": unknown light kind " + std::to_string(kind) + which + " (PSDR_LIGHT_POINT or PSDR_LIGHT_DISTANT)");
+    if (kind != PSDR_LIGHT_DISTANT || v == nullptr) return 0;
+    if (!(std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]))) return fail(std::string(fn) + ": the direction" + which + " is not finite");
+    if (v[0] == 0.f && v[1] == 0.f && v[2] == 0.f) return fail(std::string(fn) + ": the direction" + which + " is all zero");
+    return 0;
+}
+
+int psdr_scene_set_light(psdr_scene_t h, int32_t kind, const float v[3], int32_t K, const float *d_v, float *g_v) {
+    if (!h) return fail("psdr_scene_set_light: null handle");
+    if (int rc = check_light_vector("psdr_scene_set_light", kind, v, "")) return rc;
+    if (int rc = psdr_scene_set_point_light(h, v, K, d_v, g_v)) return rc;
+    if (v != nullptr) h->point_kind = kind;
+    return 0;
+}
+
+int psdr_scene_set_lights(psdr_scene_t h, int32_t L, const int32_t *kinds, const float *v, int32_t K, const float *d_v, float *g_v) {
+    if (!h) return fail("psdr_scene_set_lights: null handle");
+    const bool some = v != nullptr && L != 0;
+    if (some && kinds == nullptr) return fail("psdr_scene_set_lights: null kinds");
+    if (some && L >= 1 && L <= PSDR_POINT_LIGHTS_MAX)
+        for (int l = 0; l < L; ++l)
+            if (int rc = check_light_vector("psdr_scene_set_lights", kinds[l], v + 3 * l, " of light " + std::to_string(l))) return rc;
+    if (int rc = psdr_scene_set_point_lights(h, L, v, K, d_v, g_v)) return rc;
+    if (some) h->stack_kind.assign(kinds, kinds + L);
     return 0;
 }
 

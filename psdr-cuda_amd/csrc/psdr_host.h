@@ -311,12 +311,14 @@ struct psdr_scene_s {
     float point_pos[3] = {0.f, 0.f, 0.f}, point_dpos[3][3] = {};
     int point_K = 0;
     float *point_gpos = nullptr;
+    int point_kind = PSDR_LIGHT_POINT;     // PSDR_LIGHT_DISTANT (psdr_scene_set_light): point_pos is the direction towards the light
     // the lights of PSDR_INTEGRATOR_POINT_STACK (psdr_scene_set_point_lights), independent of the light above: host copies of the positions [L][3] and of
     // the K tangents of them [K][L][3], the caller's device gradient [L][3], and the device table the kernels read (positions, then tangents; written on
     // the call's stream before the launch)
     std::vector<float> stack_pos, stack_dpos;
     int stack_K = 0;
     float *stack_gpos = nullptr;
+    std::vector<int32_t> stack_kind;       // [L] light models (psdr_scene_set_lights); on the device behind the tangents, uploaded when a light is distant
     float *d_stack_lights = nullptr;
     size_t cap_stack_lights = 0;           // in lights
 };
@@ -403,8 +405,9 @@ struct PointLightOps {
     int (*render_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s);
     int (*render_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, float *out_img, const psdr_grads *grads, hipStream_t s);
     // the primary-edge and shadow-boundary terms alone, for a light given by value (the LightStageIntegrator launches them once per light of its stack)
-    int (*edges_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, const float *pos, const float *d_pos, float *dimg, long long plane, hipStream_t s);
-    int (*edges_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, const float *pos, float *g_pos, hipStream_t s);
+    // (kind: the light's model, PSDR_LIGHT_*)
+    int (*edges_fwd)(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, int kind, const float *pos, const float *d_pos, float *dimg, long long plane, hipStream_t s);
+    int (*edges_rev)(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, int kind, const float *pos, float *g_pos, hipStream_t s);
 };
 const PointLightOps *point_light_ops_0();
 const PointLightOps *point_light_ops_1();

@@ -15,8 +15,10 @@
 
 namespace psdr {
 
-// The lights as the kernels read them: positions [L][3] and, in forward mode, tangents [K][L][3] (null: none); read with a wave-uniform index
-struct LightTable { const float *pos; const float *dpos; int L; };
+// The lights as the kernels read them: positions [L][3] (a distant light's row: its direction), in forward mode tangents [K][L][3] (null: none) and the
+// light models [L] (PSDR_LIGHT_*; null: every light is a point light); read with a wave-uniform index, so the branch on a light's kind is wave-uniform
+struct LightTable { const float *pos; const float *dpos; int L; const int32_t *kind; };
+PSDR_HD bool stack_light_distant(const LightTable &lt, int l) { return lt.kind != nullptr && lt.kind[l] == PSDR_LIGHT_DISTANT; }
 template <int K> PSDR_HD PointLight stack_light(const LightTable &lt, int l) {
     PointLight pl{};
     for (int c = 0; c < 3; ++c) pl.p[c] = lt.pos[3 * l + c];
@@ -45,16 +47,15 @@ PSDR_HD StackHit<G> stack_camera_hit(const SceneView &sc, const TVT &tv, Travers
     return h;
 }
 // the light part of li_point, non-finite components zeroed as point_camera_sample does
-template <class G, class M, class TVT>
+template <class G, class M, int LK = kLightPoint, class TVT>
 PSDR_HD Vec3<M> stack_light_value(const SceneView &sc, const TVT &tv, TraversalStack &st, const Bsdf<G, M> &bsdf, const Its<G> &its, const PointLight &pl, uint32_t &nrays) {
-    const Vec3<G> dv = point_light_pos<G>(pl) - its.p;
-    const G r2 = dot(dv, dv);
-    const G r = sqrt_(r2);
-    const Vec3<G> dn = dv / r;
+    Vec3<G> dv, dn; G r2, r;
+    light_from<LK>(pl, its.p, dv, dn, r2, r);
     const Vec3<G> wo = its.sh.to_local(dn);
     const Vec3<M> f = colloc_bsdf_eval<TVT::has_rough>(sc, tv, bsdf, its, wo);
     if (!point_light_visible<TVT::flags>(sc, st, val(its.p), val(dn), val(r), nrays)) return zero3<M>();
-    return zero_nonfinite(f * to_m<M>(1.f / r2));
+    if constexpr (LK == kLightDistant) return zero_nonfinite(f);
+    else return zero_nonfinite(f * to_m<M>(1.f / r2));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------- reverse
@@ -113,14 +114,14 @@ PSDR_HD void stack_rev_begin(StackRevHit &H, const SceneView &sc, TraversalStack
 }
 // One light of a slot with H.ok.  adj = dLoss / d(pixel of this light's plane) / spp; returns the primal sample value; a_pl (+=): the light's gradient.
 // sink: CameraSinkOf<GEO, RealSink> over the slot's PrimaryGrad pg (pg.tri: the hit's row, once a light reaches it); brev: BsdfRev<Sink> of H.bsdf_id.
-template <bool GEO, class Sink>
+template <bool GEO, int LK = kLightPoint, class Sink>
 PSDR_HD Vec3f stack_rev_light(Sink &sink, PrimaryGrad &pg, const SceneView &sc, TraversalStack &st, const BsdfRev<Sink> &brev, StackRevHit &H, const PointLight &pl, const Vec3f &adj, uint32_t &nrays,
                               Vec3f &a_pl) {
     const TangentView<0, Sink::flags> tv0{};
     const Its<float> &its = H.its;
-    const Vec3f dv = point_light_pos<float>(pl) - its.p;
-    const float r2 = dot(dv, dv), r = sqrtf(r2), inv_r2 = 1.f / r2;
-    const Vec3f dn = dv / r;
+    Vec3f dv, dn; float r2, r;
+    light_from<LK>(pl, its.p, dv, dn, r2, r);
+    const float inv_r2 = LK == kLightDistant ? 1.f : 1.f / r2;
     const Vec3f wo = its.sh.to_local(dn);
     const Vec3f f = colloc_bsdf_eval<(Sink::flags & kSceneRough) != 0>(sc, tv0, brev.b, its, wo);
     if (!point_light_visible<Sink::flags>(sc, st, its.p, dn, r, nrays)) return Vec3f(0.f);
@@ -132,14 +133,17 @@ PSDR_HD Vec3f stack_rev_light(Sink &sink, PrimaryGrad &pg, const SceneView &sc, 
     Vec3f a_wo(0.f);
     colloc_bsdf_eval_vjp(sink, sc, tv0, brev, its, wo, a * inv_r2, H.va0.wi, a_wo, H.va0.u, H.va0.v, H.nx);
     if (GEO) {
-        // 1 / r^2 and wo = to_local(dn), dn = dv / r, dv = pL - p
-        const float a_r2 = -dot(a, zero_nonfinite(f)) * inv_r2 * inv_r2;
-        Vec3f a_dv = dv * (2.f * a_r2);
+        // 1 / r^2 and wo = to_local(dn), dn = dv / r, dv = pL - p (distant: dn = dv / |dv|, dv = d)
+        Vec3f a_dv(0.f);
+        if constexpr (LK != kLightDistant) {
+            const float a_r2 = -dot(a, zero_nonfinite(f)) * inv_r2 * inv_r2;
+            a_dv = dv * (2.f * a_r2);
+        }
         const Vec3f a_dn = its.sh.s * a_wo.x + its.sh.t * a_wo.y + its.sh.n * a_wo.z;
         acc(H.va0.s, dn * a_wo.x); acc(H.va0.t, dn * a_wo.y); acc(H.va0.n, dn * a_wo.z);
         acc_finite(a_dv, normalize_vjp(dv, dn, a_dn));
         acc_finite(a_pl, a_dv);
-        acc(H.va0.p, -a_dv);
+        if constexpr (LK != kLightDistant) acc(H.va0.p, -a_dv);
     }
     return zero_nonfinite(result);
 }

@@ -4,6 +4,9 @@
 // of the handle's device table (LightTable: read with a wave-uniform index); every light has its own wave_segmented_sum and its own plane of the output.
 // The primary-edge and shadow-boundary terms are the PointLightIntegrator's kernels (PointLightOps::edges_fwd / edges_rev), launched once per light with the
 // light's planes: the same rng_offset for every light, so every plane is the single-light launch's plane.
+// Light models (psdr_pointlight.h): the camera kernels have a last template parameter MIXED.  false: every light of the stack is a point light -- the loop
+// holds the point instantiation alone.  true: a light of the table is distant -- the loop branches, wave-uniformly, on the light's kind to one of the two
+// instantiations; a stack may mix the kinds in any order.  The host picks per launch (upload_lights).
 #ifndef PSDR_WIDE_TREE
 #if PSDR_VARIANT_FLAGS == 6
 #define PSDR_WIDE_TREE 1
@@ -31,10 +34,14 @@ namespace {
 
 // Resident waves per SIMD, chosen from the compiler's resource report of THESE kernels (profiles/lightstage_resources.txt): no instance spills a VGPR or
 // uses scratch at its bound.  The hit stays alive across the loop over the lights, so some counts are below k_point_camera's.
-template <class G, class R, int FL> constexpr int stack_camera_waves() {
+// MIXED (the loop branches on the light's kind, profiles/distantlight_resources.txt): the point-only instances keep every count; the mixed ones fit them
+// all but two -- renderC on the two-level Lambertian set (8 VGPRs spilt at eight waves: seven) and the K = 3 material duals on the plain sets 0 and 1
+// (one VGPR spilt at four waves: three).
+template <class G, class R, int FL, bool MIXED> constexpr int stack_camera_waves() {
     constexpr bool rough = (FL & kSceneRough) != 0, forest = (FL & kSceneForest) != 0;
-    if (!is_ad<R>()) return rough ? (forest ? 4 : 5) : 8;                  // renderC
+    if (!is_ad<R>()) return rough ? (forest ? 4 : 5) : ((MIXED && forest) ? 7 : 8);                  // renderC
     constexpr int K = ad_traits<R>::K;
+    if (!is_ad<G>() && MIXED && K == 3 && (FL & ~kSceneEnv) == 0) return 3;
     if (!is_ad<G>()) return K == 1 ? (rough ? 3 : 6) : (rough ? 2 : 4);   // material duals
     return K == 1 ? (rough ? (forest ? 2 : 3) : 4) : (rough ? 1 : 2);     // geometry duals
 }
@@ -44,8 +51,8 @@ template <int FL, bool GEO> constexpr int stack_rev_waves() {
 }
 
 // ---------------------------------------------------------------------- camera kernel: img [L][plane], dimg [K][L][plane]
-template <class G, class R, int FL>
-__global__ __launch_bounds__(kBlock, (stack_camera_waves<G, R, FL>())) void k_stack_camera(LaunchCtx cx, TV<R, FL> tv, LightTable lt, int spp, int s_begin, SlotDiv nsp, long long n, float inv_spp,
+template <class G, class R, int FL, bool MIXED>
+__global__ __launch_bounds__(kBlock, (stack_camera_waves<G, R, FL, MIXED>())) void k_stack_camera(LaunchCtx cx, TV<R, FL> tv, LightTable lt, int spp, int s_begin, SlotDiv nsp, long long n, float inv_spp,
                                                                                         float *__restrict__ img, float *__restrict__ dimg, long long plane,
                                                                                         unsigned long long *counters, int own) {
     constexpr int K = ad_traits<R>::K;
@@ -69,7 +76,9 @@ __global__ __launch_bounds__(kBlock, (stack_camera_waves<G, R, FL>())) void k_st
 #pragma unroll
             for (int i = 0; i < NV; ++i) v[i] = 0.f;
             if (hit.ok) {
-                const Vec3<R> r = stack_light_value<G, R>(cx.sc, tv, st, bsdf, hit.its, stack_light<KG>(lt, l), nrays);
+                const PointLight pl = stack_light<KG>(lt, l);
+                const Vec3<R> r = (MIXED && stack_light_distant(lt, l)) ? stack_light_value<G, R, kLightDistant>(cx.sc, tv, st, bsdf, hit.its, pl, nrays)
+                                                                        : stack_light_value<G, R, kLightPoint>(cx.sc, tv, st, bsdf, hit.its, pl, nrays);
                 v[0] = val(r.x) * inv_spp; v[1] = val(r.y) * inv_spp; v[2] = val(r.z) * inv_spp;
 #pragma unroll
                 for (int k = 0; k < K; ++k) { v[3 + 3 * k] = tangent(r.x, k) * inv_spp; v[4 + 3 * k] = tangent(r.y, k) * inv_spp; v[5 + 3 * k] = tangent(r.z, k) * inv_spp; }
@@ -103,7 +112,7 @@ __global__ __launch_bounds__(kBlock, (stack_camera_waves<G, R, FL>())) void k_st
 // ---------------------------------------------------------------------- reverse camera kernel: adj_img [L][plane], img [L][plane] or null, g_pos [L][3] or null
 // The lights' gradients: the wave's total per light and component (wave_total), added to a column of 3 L floats in LDS (off_gpos: behind the gradient
 // cache); one global atomic per workgroup, light and component at the end.
-template <int FL, bool GEO>
+template <int FL, bool GEO, bool MIXED>
 __global__ __launch_bounds__(kBlock, (stack_rev_waves<FL, GEO>())) void k_stack_camera_rev(LaunchCtx cx, DeviceSink<FL> sink, LightTable lt, float *g_pos, int off_gpos, int spp, int s_begin, SlotDiv nsp,
                                                                                         long long n, float inv_spp, const float *__restrict__ adj_img, float *__restrict__ img, long long plane,
                                                                                         unsigned long long *counters) {
@@ -134,7 +143,10 @@ __global__ __launch_bounds__(kBlock, (stack_rev_waves<FL, GEO>())) void k_stack_
             Vec3f r(0.f), a_pl(0.f);
             if (H.ok) {
                 const float *a = adj_img + (size_t) l * plane + (size_t) pixel * 3;
-                r = stack_rev_light<GEO>(csink, pg, cx.sc, st, brev, H, stack_light<1>(LightTable{lt.pos, nullptr, L}, l), Vec3f{a[0] * inv_spp, a[1] * inv_spp, a[2] * inv_spp}, nrays, a_pl);
+                const PointLight pl = stack_light<1>(LightTable{lt.pos, nullptr, L, nullptr}, l);
+                const Vec3f adj{a[0] * inv_spp, a[1] * inv_spp, a[2] * inv_spp};
+                r = (MIXED && stack_light_distant(lt, l)) ? stack_rev_light<GEO, kLightDistant>(csink, pg, cx.sc, st, brev, H, pl, adj, nrays, a_pl)
+                                                          : stack_rev_light<GEO, kLightPoint>(csink, pg, cx.sc, st, brev, H, pl, adj, nrays, a_pl);
             }
             if (want_gpos) {
                 // every lane of the wave arrives here
@@ -178,12 +190,18 @@ __global__ __launch_bounds__(kBlock, (stack_rev_waves<FL, GEO>())) void k_stack_
 }
 
 // ============================================================================ launches
-// The handle's lights onto the device table, on the call's stream: positions [L][3], then K tangent sets [K][L][3] (missing sets are zero)
+// The handle's lights onto the device table, on the call's stream: positions [L][3], then K tangent sets [K][L][3] (missing sets are zero); behind room for
+// three sets the kinds [L], uploaded only when a light is distant (lt.kind != null: the MIXED kernels)
 int upload_lights(psdr_scene_s *h, int K, hipStream_t s, LightTable &lt, bool &moves) {
     const int L = (int) (h->stack_pos.size() / 3);
     const size_t n3 = (size_t) L * 3;
     HIP_TRY(hipMemcpyAsync(h->d_stack_lights, h->stack_pos.data(), sizeof(float) * n3, hipMemcpyHostToDevice, s));
-    lt.pos = h->d_stack_lights; lt.dpos = nullptr; lt.L = L;
+    lt.pos = h->d_stack_lights; lt.dpos = nullptr; lt.L = L; lt.kind = nullptr;
+    if (std::find(h->stack_kind.begin(), h->stack_kind.end(), PSDR_LIGHT_DISTANT) != h->stack_kind.end()) {
+        int32_t *d_kind = reinterpret_cast<int32_t *>(h->d_stack_lights + 4 * n3);
+        HIP_TRY(hipMemcpyAsync(d_kind, h->stack_kind.data(), sizeof(int32_t) * (size_t) L, hipMemcpyHostToDevice, s));
+        lt.kind = d_kind;
+    }
     moves = false;
     const int Kh = std::min(K, h->stack_K);
     for (size_t i = 0; i < n3 * (size_t) Kh; ++i) moves = moves || h->stack_dpos[i] != 0.f;
@@ -205,8 +223,12 @@ int stack_run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL>
     const long long n = WH * nsp;
     h->slots[0] += (uint64_t) n;
     const int own = wave_owns_pixels(h, nsp, n);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stack_camera<G, R, FL>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, lt, o->spp, o->spp_begin,
-                       SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
+    if (lt.kind != nullptr)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stack_camera<G, R, FL, true>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, lt, o->spp, o->spp_begin,
+                           SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stack_camera<G, R, FL, false>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, lt, o->spp, o->spp_begin,
+                           SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -238,7 +260,7 @@ int stack_render_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_ta
     for (int l = 0; l < L; ++l) {
         float dp[3][3] = {};
         for (int k = 0; k < Kh; ++k) for (int c = 0; c < 3; ++c) dp[k][c] = h->stack_dpos[((size_t) k * L + l) * 3 + c];
-        if (int rc = point->edges_fwd(h, o, K, tangents, h->stack_pos.data() + 3 * l, &dp[0][0], dimg + (size_t) l * WH * 3, (long long) L * WH * 3, s)) return rc;
+        if (int rc = point->edges_fwd(h, o, K, tangents, h->stack_kind[(size_t) l], h->stack_pos.data() + 3 * l, &dp[0][0], dimg + (size_t) l * WH * 3, (long long) L * WH * 3, s)) return rc;
     }
     return 0;
 }
@@ -277,16 +299,17 @@ int stack_render_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *ad
         dyn_bytes = off_gpos + (geo && g_pos ? 3 * L * (int) sizeof(float) : 0);
         if (dyn_bytes > h->lds_limit) return fail("psdr_render_d_rev: the LightStageIntegrator's launch needs " + std::to_string(dyn_bytes) + " bytes of LDS per workgroup, the device offers " +
                                                   std::to_string(h->lds_limit));
-#define PSDR_LAUNCH_STACK_REV(GEO)                                                                                                                                       \
-        do { if (int rc = allow_dynamic_lds(&k_stack_camera_rev<FL, GEO>, dyn_bytes)) return rc;                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stack_camera_rev<FL, GEO>), dim3(launch_blocks(h, n)), dim3(kBlock), dyn_bytes, s, cx, sink, lt, g_pos, off_gpos, o->spp, o->spp_begin, SlotDiv(nsp), n,       \
+#define PSDR_LAUNCH_STACK_REV(GEO, MIXED)                                                                                                                                \
+        do { if (int rc = allow_dynamic_lds(&k_stack_camera_rev<FL, GEO, MIXED>, dyn_bytes)) return rc;                                                                  \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stack_camera_rev<FL, GEO, MIXED>), dim3(launch_blocks(h, n)), dim3(kBlock), dyn_bytes, s, cx, sink, lt, g_pos, off_gpos, o->spp, o->spp_begin, SlotDiv(nsp), n, \
                            1.f / (float) o->spp, adj_img, out_img, WH * 3, h->d_counters); } while (0)
-        if (geo) PSDR_LAUNCH_STACK_REV(true); else PSDR_LAUNCH_STACK_REV(false);
+        if (lt.kind != nullptr) { if (geo) PSDR_LAUNCH_STACK_REV(true, true); else PSDR_LAUNCH_STACK_REV(false, true); }
+        else { if (geo) PSDR_LAUNCH_STACK_REV(true, false); else PSDR_LAUNCH_STACK_REV(false, false); }
 #undef PSDR_LAUNCH_STACK_REV
         HIP_TRY(hipGetLastError());
     }
     for (int l = 0; l < L; ++l)
-        if (int rc = point->edges_rev(h, o, adj_img + (size_t) l * WH * 3, grads, h->stack_pos.data() + 3 * l, g_pos ? g_pos + 3 * l : nullptr, s)) return rc;
+        if (int rc = point->edges_rev(h, o, adj_img + (size_t) l * WH * 3, grads, h->stack_kind[(size_t) l], h->stack_pos.data() + 3 * l, g_pos ? g_pos + 3 * l : nullptr, s)) return rc;
     return 0;
 }
 }  // namespace

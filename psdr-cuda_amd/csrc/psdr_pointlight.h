@@ -7,15 +7,22 @@
 // slot, three per shadow-boundary slot (the first is used).
 // The geometry gradient has three terms: the interior (dual numbers through its.p, the frame, wi, wo, r^2 and pL), the primary edges (collocated_edge_values
 // with this Li on both sides) and the boundary of the moving shadow outline (point_sedge_*), which the collocated configuration never sees.
-// ONE copy of the estimator: the forward kernels, the reverse kernels (psdr_pointlight.hip) and the host harness (tests/hostcheck/hostcheck_pointlight.cpp)
-// instantiate the functions below.
+// ONE copy of the estimator: the forward kernels, the reverse kernels (psdr_pointlight.hip) and the host harnesses (tests/hostcheck/hostcheck_pointlight.cpp,
+// hostcheck_distantlight.cpp) instantiate the functions below.
+// The light model is a compile-time parameter LK of them (include/psdr_hip.h: PSDR_LIGHT_POINT, the default, is the text above).  PSDR_LIGHT_DISTANT: the
+// PointLight's vector is a direction d from the scene TOWARDS the light, of any length; with u = d / |d| and wo = its.sh.to_local(u)
+//     Li = f(its; wi = its.wi, wo) * V(its.p, u)                 (0 on a miss)
+// V = 1 unless the walk finds a hit with t in [RayEpsilon, inf) on the ray (its.p, u); no falloff: unit IRRADIANCE on a surface that faces the light, so a
+// point light at c + R u with intensity R^2 tends to this model.  The gradient is that of d as passed: tangential, and 1 / |d| in size.  The shadow
+// boundary is a parallel projection (point_sedge_values).
 #pragma once
 #include "psdr_collocated.h"
 
 namespace psdr {
 
-// The light as the kernels receive it: position and, in forward mode, its K tangents (zero otherwise)
+// The light as the kernels receive it: position (PSDR_LIGHT_DISTANT: direction towards the light) and, in forward mode, its K tangents (zero otherwise)
 struct PointLight { float p[3]; float d[3][3]; };
+constexpr int kLightPoint = PSDR_LIGHT_POINT, kLightDistant = PSDR_LIGHT_DISTANT;
 template <class G> PSDR_HD Vec3<G> point_light_pos(const PointLight &pl) {
     Vec3<G> p = lift<G>(Vec3f{pl.p[0], pl.p[1], pl.p[2]});
     if constexpr (is_ad<G>()) {
@@ -31,48 +38,64 @@ PSDR_HD bool point_light_visible(const SceneView &sc, TraversalStack &st, const 
     return closest_hit<false, tree_mode<FL>()>(sc, st, p, d0, r - kShadowEpsilon).tri < 0;
 }
 
+// The light seen from p: the unit direction dn towards it, the far end tmax of the visibility ray and, for the point model alone, dv = pL - p and r^2
+// (the distant model leaves dv = d, for normalize_vjp, and r2 unset)
+template <int LK, class G> PSDR_HD void light_from(const PointLight &pl, const Vec3<G> &p, Vec3<G> &dv, Vec3<G> &dn, G &r2, G &r) {
+    if constexpr (LK == kLightDistant) {
+        dv = point_light_pos<G>(pl);
+        dn = normalize(dv);
+        r = G(INFINITY);
+    } else {
+        dv = point_light_pos<G>(pl) - p;
+        r2 = dot(dv, dv);
+        r = sqrt_(r2);
+        dn = dv / r;
+    }
+}
+
 // Li of one camera ray.  G: geometry type (Dual<K>: the solid-angle form of the hit, and the light's tangents), M: material / result type.
-template <class G, class M, bool KNOWN = false, class TVT>
+template <class G, class M, bool KNOWN = false, int LK = kLightPoint, class TVT>
 PSDR_HD Vec3<M> li_point(const SceneView &sc, const TVT &tv, TraversalStack &st, const PointLight &pl, const RayT<G> &ray, bool active, uint32_t &nrays, const Hit *primary = nullptr) {
     const Its<G> its = known_or_traced<KNOWN, G>(sc, tv, st, ray, active, nrays, primary);
     if (!(active && its.valid)) return zero3<M>();
     const int bsdf_id = Tab<TVT::flags>::mesh_bsdf(sc, its.mesh);
     if (bsdf_id < 0) return zero3<M>();          // the bounding mesh of an environment map has no BSDF
-    const Vec3<G> dv = point_light_pos<G>(pl) - its.p;
-    const G r2 = dot(dv, dv);
-    const G r = sqrt_(r2);
-    const Vec3<G> dn = dv / r;
+    Vec3<G> dv, dn; G r2, r;
+    light_from<LK>(pl, its.p, dv, dn, r2, r);
     const Vec3<G> wo = its.sh.to_local(dn);
     const Bsdf<G, M> bsdf(sc, tv, bsdf_id);
     const Vec3<M> f = colloc_bsdf_eval<TVT::has_rough>(sc, tv, bsdf, its, wo);
     if (!point_light_visible<TVT::flags>(sc, st, val(its.p), val(dn), val(r), nrays)) return zero3<M>();
-    return f * to_m<M>(1.f / r2);
+    if constexpr (LK == kLightDistant) return f;
+    else return f * to_m<M>(1.f / r2);
 }
 
 // One camera sample slot (collocated_camera_sample's counterpart)
-template <class G, class M, class TVT>
+template <class G, class M, int LK = kLightPoint, class TVT>
 PSDR_HD Vec3<M> point_camera_sample(const SceneView &sc, const TVT &tv, TraversalStack &st, const PointLight &pl, const RngJump &jump, int pixel, uint64_t slot, uint32_t &nrays) {
     Rng rng; rng.init(slot, jump);
     const float j0 = rng.next(), j1 = rng.next();
     const int W = sc.d.width;
     const float sx = ((float) (pixel % W) + j0) / (float) W, sy = ((float) (pixel / W) + j1) / (float) sc.d.height;
     const RayT<G> ray = primary_ray<G>(sc, tv, sx, sy);
-    return zero_nonfinite(li_point<G, M>(sc, tv, st, pl, ray, true, nrays));
+    return zero_nonfinite(li_point<G, M, false, LK>(sc, tv, st, pl, ray, true, nrays));
 }
 
 // The Li of the primary-edge term: collocated_edge_values / _sample / _reverse_values (psdr_collocated.h) take it as their LiOf
-struct PointLi {
+template <int LK> struct PointLiOf {
     PointLight pl;
     template <bool KNOWN, class TVT>
     PSDR_HD Vec3f at(const SceneView &sc, const TVT &tv0, TraversalStack &st, const RayT<float> &ray, bool active, uint32_t &nrays, const Hit *primary) const {
-        return li_point<float, float, KNOWN>(sc, tv0, st, pl, ray, active, nrays, primary);
+        return li_point<float, float, KNOWN, LK>(sc, tv0, st, pl, ray, active, nrays, primary);
     }
 };
+using PointLi = PointLiOf<kLightPoint>;
 
 // One camera sample in reverse mode (collocated_sample_reverse's sibling).  adj = dLoss / d(pixel) / spp; returns the primal sample value.
 //   GEO: a geometry gradient (triangle table / camera / light position) is wanted -> the solid-angle form of the hit and its adjoint chain
-// The a_wo that colloc_bsdf_eval_vjp returns goes through wo = to_local(dv / r) to its.p, the frame and pL (a_pl, +=).
-template <bool GEO, class RealSink>
+// The a_wo that colloc_bsdf_eval_vjp returns goes through wo = to_local(dv / r) to its.p, the frame and pL (a_pl, +=); under the distant model through
+// wo = to_local(d / |d|) to the frame and d (a_pl, +=: tangential, 1 / |d| in size), and nothing reaches its.p.
+template <bool GEO, int LK = kLightPoint, class RealSink>
 PSDR_HD Vec3f point_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, const SceneView &sc, TraversalStack &st, const PointLight &pl, const RngJump &jump, int pixel, uint64_t slot,
                                    const Vec3f &adj, uint32_t &nrays, Vec3f &a_pl) {
     pg.clear();
@@ -111,9 +134,9 @@ PSDR_HD Vec3f point_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, const S
 
     const int bsdf_id = Tab<RealSink::flags>::mesh_bsdf(sc, its.mesh);
     if (bsdf_id < 0) return Vec3f(0.f);
-    const Vec3f dv = point_light_pos<float>(pl) - its.p;
-    const float r2 = dot(dv, dv), r = sqrtf(r2), inv_r2 = 1.f / r2;
-    const Vec3f dn = dv / r;
+    Vec3f dv, dn; float r2, r;
+    light_from<LK>(pl, its.p, dv, dn, r2, r);
+    const float inv_r2 = LK == kLightDistant ? 1.f : 1.f / r2;
     const Vec3f wo = its.sh.to_local(dn);
     BsdfRev<Sink> brev(sc, bsdf_id);
     const Vec3f f = colloc_bsdf_eval<(Sink::flags & kSceneRough) != 0>(sc, tv0, brev.b, its, wo);
@@ -128,14 +151,17 @@ PSDR_HD Vec3f point_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, const S
     colloc_bsdf_eval_vjp(sink, sc, tv0, brev, its, wo, a * inv_r2, va0.wi, a_wo, va0.u, va0.v, nx);
     constexpr bool kNormalMaps = (Sink::flags & kSceneRough) != 0;       // (the type is compiled into the rough flag sets only)
     if (GEO) {
-        // 1 / r^2 and wo = to_local(dn), dn = dv / r, dv = pL - p
-        const float a_r2 = -dot(a, zero_nonfinite(f)) * inv_r2 * inv_r2;
-        Vec3f a_dv = dv * (2.f * a_r2);
+        // 1 / r^2 and wo = to_local(dn), dn = dv / r, dv = pL - p (distant: dn = dv / |dv|, dv = d)
+        Vec3f a_dv(0.f);
+        if constexpr (LK != kLightDistant) {
+            const float a_r2 = -dot(a, zero_nonfinite(f)) * inv_r2 * inv_r2;
+            a_dv = dv * (2.f * a_r2);
+        }
         const Vec3f a_dn = its.sh.s * a_wo.x + its.sh.t * a_wo.y + its.sh.n * a_wo.z;
         acc(va0.s, dn * a_wo.x); acc(va0.t, dn * a_wo.y); acc(va0.n, dn * a_wo.z);
         acc_finite(a_dv, normalize_vjp(dv, dn, a_dn));
         acc_finite(a_pl, a_dv);
-        acc(va0.p, -a_dv);
+        if constexpr (LK != kLightDistant) acc(va0.p, -a_dv);
         // the primary vertex: wi = to_local(-d), frame(sh_n(bu, bv)), uv(bu, bv), p = p0 + bu e1 + bv e2, (bu, bv, t) = MT(tri0, ray)
         const Vec3f dcam = camera_space_dir(sc, sx, sy);
         const Vec3f a_d = -(its.sh.s * va0.wi.x + its.sh.t * va0.wi.y + its.sh.n * va0.wi.z);
@@ -162,9 +188,12 @@ PSDR_HD Vec3f point_sample_reverse(RealSink &real_sink, PrimaryGrad &pg, const S
 //     sensor_val * |dot(to camera, nD)| * f(xD; wi = to the camera, wo = to pL) / rD^2
 // (sample_direct's sensor_val is per solid angle of the camera: the cosine at xD turns it into a density per area; f carries the shading cosine to the
 // light, as in Li, so the shading-normal factor of secondary_edge_sample reduces to that geometric cosine).
+// PSDR_LIGHT_DISTANT: the projection is parallel, along -u.  The segment runs from infinity through xB onto xD; an edge element maps to (sinphi / sinphi2) dl
+// of outline (rD / rB -> 1, and the 1 / rD^2 is gone with the falloff); (u, v) = Moeller-Trumbore of the ray (xB, -u), so the outline moves with the edge
+// row through the ray's ORIGIN and with d through its direction -- a different Jacobian and a different motion term, not a limit of the ones above.
 // What forward and reverse mode share; false: the slot contributes nothing.
 struct PointSedge { int k, pixel, tri; float s1; Vec3f xB, n; float value0[3]; };
-template <int FL>
+template <int FL, int LK = kLightPoint>
 PSDR_HD bool point_sedge_values(const SceneView &sc, TraversalStack &st, const PointLight &pl, const float s3[3], uint32_t &nrays, PointSedge &r) {
     const TangentView<0, FL> tv0{};
     float s1 = s3[0], pmf;
@@ -177,10 +206,10 @@ PSDR_HD bool point_sedge_values(const SceneView &sc, TraversalStack &st, const P
     if (!(pmf > 0.f && e1len > 0.f)) return false;          // a dropped row of a capacity table
     const Vec3f edge = ee1 / e1len, edge2 = ep2 - ep0;
     const float pdf = pmf / e1len;
-    const Vec3f pL = point_light_pos<float>(pl);
-    const Vec3f wv = xB - pL;
-    const float rB = norm(wv);
-    const Vec3f dir = wv / rB;
+    const Vec3f pL = point_light_pos<float>(pl);          // (distant: d)
+    Vec3f dir; float rB;
+    if constexpr (LK == kLightDistant) { dir = -normalize(pL); rB = INFINITY; }
+    else { const Vec3f wv = xB - pL; rB = norm(wv); dir = wv / rB; }
     // the silhouette test of boundary_segment_direct with e = -dir
     const Vec3f e = -dir;
     const float d0n = dot(n0, e), d1n = dot(n1, e);
@@ -188,10 +217,11 @@ PSDR_HD bool point_sedge_values(const SceneView &sc, TraversalStack &st, const P
     if (!(rB > kShadowEpsilon && (is_boundary ? sgn0 != 0 : sgn0 * sgn1 < 0))) return false;
     const bool skip = sc.d.sec_edge_faces != nullptr;
     const int f0 = skip ? sc.d.sec_edge_faces[2 * k] : -1, f1 = skip ? sc.d.sec_edge_faces[2 * k + 1] : -1;
-    // pL -> xB unoccluded (the edge's own faces left out), then on from xB onto a surface
+    // pL -> xB unoccluded (the edge's own faces left out; distant: xB towards the light, to infinity), then on from xB onto a surface
     nrays++;
-    const Hit hb = (f0 >= 0 || f1 >= 0) ? closest_hit<true, tree_mode<FL>()>(sc, st, pL, dir, rB - kShadowEpsilon, f0, f1)
-                                        : closest_hit<false, tree_mode<FL>()>(sc, st, pL, dir, rB - kShadowEpsilon);
+    const Vec3f bo = LK == kLightDistant ? xB : pL, bd = LK == kLightDistant ? e : dir;
+    const Hit hb = (f0 >= 0 || f1 >= 0) ? closest_hit<true, tree_mode<FL>()>(sc, st, bo, bd, rB - kShadowEpsilon, f0, f1)
+                                        : closest_hit<false, tree_mode<FL>()>(sc, st, bo, bd, rB - kShadowEpsilon);
     if (hb.tri >= 0) return false;
     const Its<float> itsD = intersect<float>(sc, tv0, st, RayT<float>{xB, dir}, true, kDetached, nrays, f0, f1);
     if (!itsD.valid) return false;
@@ -204,7 +234,6 @@ PSDR_HD bool point_sedge_values(const SceneView &sc, TraversalStack &st, const P
     const Hit hc = closest_hit<false, tree_mode<FL>()>(sc, st, cam.o, cam.d, INFINITY);
     if (hc.tri < 0) return false;
     if (!(camera_return_distance(sc, itsD.tri, itsD.hu, itsD.hv, hc.tri) < (double) kShadowEpsilon)) return false;
-    const float rD = norm(xD - pL);
     const Vec3f nD = itsD.n;
     const Vec3f ev = cross(edge, dir);
     const float sinphi = norm(ev);
@@ -222,26 +251,30 @@ PSDR_HD bool point_sedge_values(const SceneView &sc, TraversalStack &st, const P
     const float correction = fabsf(dot(d0, nD));
     const Vec3f n = normalize(cross(nD, proj));
     const float sign = copysignf(1.f, dot(ev, edge2)) * copysignf(1.f, dot(ev, n));
-    const float wgt = sensor_val * correction / (rD * rD) * (rD / rB) * (sinphi / sinphi2) / pdf * sign;
+    float wgt;
+    if constexpr (LK == kLightDistant) wgt = sensor_val * correction * (sinphi / sinphi2) / pdf * sign;
+    else { const float rD = norm(xD - pL); wgt = sensor_val * correction / (rD * rD) * (rD / rB) * (sinphi / sinphi2) / pdf * sign; }
     r.k = k; r.pixel = pixel; r.tri = itsD.tri; r.s1 = s1; r.xB = xB; r.n = n;
     r.value0[0] = f.x * wgt; r.value0[1] = f.y * wgt; r.value0[2] = f.z * wgt;
     return true;
 }
 // forward mode: returns the pixel (or -1), tan[k][c] = d value / d P_k.  The triangle row at xD, the edge row and pL are differentiable; x(u, v) is
-// rebuilt from the DETACHED row (the u2 construction of secondary_edge_sample).
-template <int K, int FL>
+// rebuilt from the DETACHED row (the u2 construction of secondary_edge_sample).  Distant: the ray (bp0, -normalize(d)), origin and direction differentiable.
+template <int K, int FL, int LK = kLightPoint>
 PSDR_HD int point_sedge_sample(const SceneView &sc, const TangentView<K, FL> &tv, TraversalStack &st, const PointLight &pl, const float s3[3], float inv_sppse,
                                float tan[K][3], uint32_t &nrays) {
     using R = Dual<K>;
     PointSedge e;
-    if (!point_sedge_values<FL>(sc, st, pl, s3, nrays, e)) return -1;
+    if (!point_sedge_values<FL, LK>(sc, st, pl, s3, nrays, e)) return -1;
     const size_t off = (size_t) e.k * PSDR_SEDGE_STRIDE;
     constexpr auto sm = &psdr_tangents::d_sec_edge;
     const Vec3<R> ep0 = ld3<R>(sc.d.sec_edge, tv, sm, off), ee1 = ld3<R>(sc.d.sec_edge, tv, sm, off + 3);
     const Vec3<R> bp0 = ee1 * R(e.s1) + ep0;
     const Vec3<R> pL = point_light_pos<R>(pl);
     const TriRow<R> T = load_tri<R>(sc, tv, e.tri);
-    const RayT<R> shadow{pL, normalize(bp0 - pL)};
+    RayT<R> shadow;
+    if constexpr (LK == kLightDistant) shadow = RayT<R>{bp0, -normalize(pL)};
+    else shadow = RayT<R>{pL, normalize(bp0 - pL)};
     R u, v, t;
     moeller_trumbore(T.p0, T.e1, T.e2, shadow, u, v, t);
     const Vec3<R> u2 = bary_point(detach(T.p0), detach(T.e1), detach(T.e2), u, v);
@@ -252,17 +285,19 @@ PSDR_HD int point_sedge_sample(const SceneView &sc, const TangentView<K, FL> &tv
         for (int c = 0; c < 3; ++c) { const float g = dn.d[k] * e.value0[c]; tan[k][c] = (isfinite(e.value0[c] * dn.v) && isfinite(g)) ? g * inv_sppse : 0.f; }
     return e.pixel;
 }
-// reverse mode: adjoints to g_sec_edge (p0, e1) and g_tri_info (the row at xD) through the sink, to the light position through a_pl (+=)
-template <class Sink>
+// reverse mode: adjoints to g_sec_edge (p0, e1) and g_tri_info (the row at xD) through the sink, to the light position through a_pl (+=).  Distant: the
+// ray's origin adjoint goes to the edge row, its direction adjoint through -normalize_vjp to d; the point light routes both through xB - pL.
+template <int LK = kLightPoint, class Sink>
 PSDR_HD void point_sedge_reverse(Sink &sink, const SceneView &sc, TraversalStack &st, const PointLight &pl, const float s3[3], float inv_sppse,
                                  const float *__restrict__ adj_img, uint32_t &nrays, Vec3f &a_pl) {
     const TangentView<0, Sink::flags> tv0{};
     PointSedge e;
-    if (!point_sedge_values<Sink::flags>(sc, st, pl, s3, nrays, e)) return;
+    if (!point_sedge_values<Sink::flags, LK>(sc, st, pl, s3, nrays, e)) return;
     const Vec3f pL = point_light_pos<float>(pl);
     const TriRow<float> TA = load_tri<float>(sc, tv0, e.tri);
-    const Vec3f wv = e.xB - pL;
-    const RayT<float> shadow{pL, normalize(wv)};
+    const Vec3f wv = LK == kLightDistant ? pL : e.xB - pL;
+    const Vec3f wn = normalize(wv);
+    const RayT<float> shadow = LK == kLightDistant ? RayT<float>{e.xB, -wn} : RayT<float>{pL, wn};
     float su, sv, stt;
     moeller_trumbore(TA.p0, TA.e1, TA.e2, shadow, su, sv, stt);
     const Vec3f u2 = bary_point(TA.p0, TA.e1, TA.e2, su, sv);
@@ -276,11 +311,12 @@ PSDR_HD void point_sedge_reverse(Sink &sink, const SceneView &sc, TraversalStack
     const Vec3f a_u2 = e.n * a_dn;
     const MtAdj ma = mt_vjp(TA.p0, TA.e1, TA.e2, shadow, dot(a_u2, TA.e1), dot(a_u2, TA.e2), 0.f);
     scatter_vec(sink, e.tri, 0, ma.p0); scatter_vec(sink, e.tri, 3, ma.e1); scatter_vec(sink, e.tri, 6, ma.e2);
-    const Vec3f a_w = normalize_vjp(wv, shadow.d, ma.d);
+    const Vec3f a_wn = normalize_vjp(wv, wn, ma.d);
+    const Vec3f a_w = LK == kLightDistant ? ma.o : a_wn;
     // xB = e1 * s1 + p0 (edge table)
     sink.add_sedge(e.k, 0, a_w.x); sink.add_sedge(e.k, 1, a_w.y); sink.add_sedge(e.k, 2, a_w.z);
     sink.add_sedge(e.k, 3, a_w.x * e.s1); sink.add_sedge(e.k, 4, a_w.y * e.s1); sink.add_sedge(e.k, 5, a_w.z * e.s1);
-    acc_finite(a_pl, ma.o - a_w);
+    acc_finite(a_pl, LK == kLightDistant ? -a_wn : ma.o - a_w);
 }
 
 }  // namespace psdr

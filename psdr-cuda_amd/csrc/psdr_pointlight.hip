@@ -5,7 +5,8 @@
 // Shared with the other kernels: primary_ray, closest_hit / intersect (every scene form), the film-sample and splat machinery of k_camera (wave_segmented_sum,
 // the plain-store path of a wave that owns its pixels), wave_run_sum, Bsdf / BsdfRev, DeviceSink, PrimaryEdgeSink, begin_edge_term and the pixel-sorted slot
 // order of the primary-edge launches.  The light travels as a kernel argument (PointLight: position + tangents), its gradient leaves through one atomic per
-// wave and component (wave_total first).
+// wave and component (wave_total first).  Every kernel has the light model as its last template parameter (LK: PSDR_LIGHT_POINT / PSDR_LIGHT_DISTANT,
+// psdr_pointlight.h); the host picks the family per launch from the light's kind (PSDR_BY_KIND).
 #ifndef PSDR_WIDE_TREE
 #if PSDR_VARIANT_FLAGS == 6
 #define PSDR_WIDE_TREE 1
@@ -47,8 +48,12 @@ template <int FL, bool GEO> constexpr int point_rev_waves() {
     return GEO ? 2 : (rough ? 3 : 5);
 }
 template <int K, int FL> constexpr int point_edge_waves() { return ((FL & kSceneRough) != 0) ? 3 : 4; }       // K = 0: the reverse kernel
-// K = 0: the reverse kernel.  K = 3 at four waves (128 VGPRs) spills one VGPR on the two-level Lambertian set: three
-template <int K, int FL> constexpr int point_sedge_waves() { return ((FL & kSceneRough) != 0 || K == 3) ? 3 : 4; }
+// K = 0: the reverse kernel.  K = 3 at four waves (128 VGPRs) spills one VGPR on the two-level Lambertian set: three.  The distant family
+// (profiles/distantlight_resources.txt) fits every bound of the point family but one: K = 1 on the plain sets 0 and 1 spills one VGPR at four waves: three
+template <int K, int FL, int LK> constexpr int point_sedge_waves() {
+    if (LK == PSDR_LIGHT_DISTANT && K == 1 && (FL & ~kSceneEnv) == 0) return 3;
+    return ((FL & kSceneRough) != 0 || K == 3) ? 3 : 4;
+}
 
 __device__ __forceinline__ void add_light_grad(float *g_pos, const Vec3f &a) {
     // every lane of the wave arrives here: the wave's total, then one atomic per component
@@ -61,7 +66,7 @@ __device__ __forceinline__ void add_light_grad(float *g_pos, const Vec3f &a) {
 }
 
 // ---------------------------------------------------------------------- camera kernel (k_colloc_camera with this estimator)
-template <class G, class R, int FL>
+template <class G, class R, int FL, int LK>
 __global__ __launch_bounds__(kBlock, (point_camera_waves<G, R, FL>())) void k_point_camera(LaunchCtx cx, TV<R, FL> tv, PointLight pl, int spp, int s_begin, SlotDiv nsp, long long n, float inv_spp,
                                                                                         float *__restrict__ img, float *__restrict__ dimg, long long plane,
                                                                                         unsigned long long *counters, int own) {
@@ -79,7 +84,7 @@ __global__ __launch_bounds__(kBlock, (point_camera_waves<G, R, FL>())) void k_po
         for (int i = 0; i < NV; ++i) v[i] = 0.f;
         if (in) {
             const uint64_t slot = (uint64_t) pixel * (uint64_t) spp + (uint64_t) (s_begin + s_in);
-            const Vec3<R> r = point_camera_sample<G, R>(cx.sc, tv, st, pl, cx.jump, pixel, slot, nrays);
+            const Vec3<R> r = point_camera_sample<G, R, LK>(cx.sc, tv, st, pl, cx.jump, pixel, slot, nrays);
             v[0] = val(r.x) * inv_spp; v[1] = val(r.y) * inv_spp; v[2] = val(r.z) * inv_spp;
 #pragma unroll
             for (int k = 0; k < K; ++k) { v[3 + 3 * k] = tangent(r.x, k) * inv_spp; v[4 + 3 * k] = tangent(r.y, k) * inv_spp; v[5 + 3 * k] = tangent(r.z, k) * inv_spp; }
@@ -110,7 +115,7 @@ __global__ __launch_bounds__(kBlock, (point_camera_waves<G, R, FL>())) void k_po
 }
 
 // ---------------------------------------------------------------------- reverse camera kernel
-template <int FL, bool GEO>
+template <int FL, bool GEO, int LK>
 __global__ __launch_bounds__(kBlock, (point_rev_waves<FL, GEO>())) void k_point_camera_rev(LaunchCtx cx, DeviceSink<FL> sink, PointLight pl, float *g_pos, int spp, int s_begin, SlotDiv nsp, long long n,
                                                                                         float inv_spp, const float *__restrict__ adj_img, float *__restrict__ img, unsigned long long *counters) {
     TraversalStack st; setup_lds(cx, st);
@@ -127,7 +132,7 @@ __global__ __launch_bounds__(kBlock, (point_rev_waves<FL, GEO>())) void k_point_
         if (in) {
             const uint64_t slot = (uint64_t) pixel * (uint64_t) spp + (uint64_t) (s_begin + s_in);
             const float *a = adj_img + (size_t) pixel * 3;
-            const Vec3f r = point_sample_reverse<GEO>(sink, pg, cx.sc, st, pl, cx.jump, pixel, slot, Vec3f{a[0] * inv_spp, a[1] * inv_spp, a[2] * inv_spp}, nrays, a_pl);
+            const Vec3f r = point_sample_reverse<GEO, LK>(sink, pg, cx.sc, st, pl, cx.jump, pixel, slot, Vec3f{a[0] * inv_spp, a[1] * inv_spp, a[2] * inv_spp}, nrays, a_pl);
             v[0] = r.x * inv_spp; v[1] = r.y * inv_spp; v[2] = r.z * inv_spp;
         }
         // primary-triangle row: one add per run of lanes that hit the same triangle
@@ -154,12 +159,12 @@ __global__ __launch_bounds__(kBlock, (point_rev_waves<FL, GEO>())) void k_point_
 }
 
 // ---------------------------------------------------------------------- primary-edge kernels (k_colloc_edge / k_colloc_edge_rev with this Li)
-template <int K, int FL>
+template <int K, int FL, int LK>
 __global__ __launch_bounds__(kBlock, (point_edge_waves<K, FL>())) void k_point_edge(LaunchCtx cx, TangentView<K, FL> tv, PointLight pl, long long i0, long long n, float inv_sppe,
                                                                               float *__restrict__ dimg, long long plane, unsigned long long *counters, const uint32_t *__restrict__ order) {
     TraversalStack st; setup_lds(cx, st);
     uint32_t nrays = 0;
-    const PointLi li{pl};
+    const PointLiOf<LK> li{pl};
     const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
     for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
         float tan[K][3];
@@ -184,12 +189,12 @@ __global__ __launch_bounds__(kBlock, (point_edge_waves<K, FL>())) void k_point_e
     }
     count_rays(counters, nrays);
 }
-template <int FL>
+template <int FL, int LK>
 __global__ __launch_bounds__(kBlock, (point_edge_waves<0, FL>())) void k_point_edge_rev(LaunchCtx cx, PrimaryEdgeSink<FL> sink, PointLight pl, long long i0, long long n, float inv_sppe,
                                                                                   const float *__restrict__ adj_img, unsigned long long *counters, const uint32_t *__restrict__ order) {
     TraversalStack st; setup_lds(cx, st);
     uint32_t nrays = 0;
-    const PointLi li{pl};
+    const PointLiOf<LK> li{pl};
     const long long nceil = (n + kBlock - 1) / kBlock * kBlock;
     for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < nceil; j += (long long) gridDim.x * kBlock) {
         float w[4] = {0.f, 0.f, 0.f, 0.f};
@@ -205,8 +210,8 @@ __global__ __launch_bounds__(kBlock, (point_edge_waves<0, FL>())) void k_point_e
 }
 
 // ---------------------------------------------------------------------- shadow-boundary kernels (slots of sampler 2)
-template <int K, int FL>
-__global__ __launch_bounds__(kBlock, (point_sedge_waves<K, FL>())) void k_point_sedge(LaunchCtx cx, TangentView<K, FL> tv, PointLight pl, long long i0, long long n, float inv_sppse,
+template <int K, int FL, int LK>
+__global__ __launch_bounds__(kBlock, (point_sedge_waves<K, FL, LK>())) void k_point_sedge(LaunchCtx cx, TangentView<K, FL> tv, PointLight pl, long long i0, long long n, float inv_sppse,
                                                                                 float *__restrict__ dimg, long long plane, unsigned long long *counters) {
     TraversalStack st; setup_lds(cx, st);
     uint32_t nrays = 0;
@@ -217,7 +222,7 @@ __global__ __launch_bounds__(kBlock, (point_sedge_waves<K, FL>())) void k_point_
         if (j < n) {
             Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
             const float s3[3] = {rng.next(), rng.next(), rng.next()};
-            pixel = point_sedge_sample<K, FL>(cx.sc, tv, st, pl, s3, inv_sppse, tan, nrays);
+            pixel = point_sedge_sample<K, FL, LK>(cx.sc, tv, st, pl, s3, inv_sppse, tan, nrays);
         }
         float v[3 * K];
 #pragma unroll
@@ -235,8 +240,8 @@ __global__ __launch_bounds__(kBlock, (point_sedge_waves<K, FL>())) void k_point_
     }
     count_rays(counters, nrays);
 }
-template <int FL>
-__global__ __launch_bounds__(kBlock, (point_sedge_waves<0, FL>())) void k_point_sedge_rev(LaunchCtx cx, DeviceSink<FL> sink, PointLight pl, float *g_pos, long long i0, long long n, float inv_sppse,
+template <int FL, int LK>
+__global__ __launch_bounds__(kBlock, (point_sedge_waves<0, FL, LK>())) void k_point_sedge_rev(LaunchCtx cx, DeviceSink<FL> sink, PointLight pl, float *g_pos, long long i0, long long n, float inv_sppse,
                                                                                     const float *__restrict__ adj_img, unsigned long long *counters) {
     TraversalStack st; setup_lds(cx, st);
     sink.begin(dyn_lds_floats(cx.off_sink));
@@ -245,7 +250,7 @@ __global__ __launch_bounds__(kBlock, (point_sedge_waves<0, FL>())) void k_point_
     for (long long j = (long long) blockIdx.x * kBlock + threadIdx.x; j < n; j += (long long) gridDim.x * kBlock) {
         Rng rng; rng.init((uint64_t) (i0 + j), cx.jump);
         const float s3[3] = {rng.next(), rng.next(), rng.next()};
-        point_sedge_reverse(sink, cx.sc, st, pl, s3, inv_sppse, adj_img, nrays, a_pl);
+        point_sedge_reverse<LK>(sink, cx.sc, st, pl, s3, inv_sppse, adj_img, nrays, a_pl);
     }
     add_light_grad(g_pos, a_pl);
     sink.end();
@@ -253,6 +258,10 @@ __global__ __launch_bounds__(kBlock, (point_sedge_waves<0, FL>())) void k_point_
 }
 
 // ============================================================================ launches
+// one statement for the light's kind: LK is the model inside it
+#define PSDR_BY_KIND(kind, ...)                                                                                    \
+    do { if ((kind) == PSDR_LIGHT_DISTANT) { constexpr int LK = PSDR_LIGHT_DISTANT; __VA_ARGS__; }                 \
+         else { constexpr int LK = PSDR_LIGHT_POINT; __VA_ARGS__; } } while (0)
 PointLight light_of(const psdr_scene_s *h, int K) {
     PointLight pl{};
     for (int c = 0; c < 3; ++c) pl.p[c] = h->point_pos[c];
@@ -267,7 +276,7 @@ bool light_moves(const psdr_scene_s *h, int K) {
 }
 
 template <class G, class R, int FL>
-int point_run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, const PointLight &pl, float *img, float *dimg, hipStream_t s) {
+int point_run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, int kind, const PointLight &pl, float *img, float *dimg, hipStream_t s) {
     const long long WH = (long long) h->desc.width * h->desc.height;
     const int nsp = o->spp_end - o->spp_begin;
     if (o->spp <= 0 || nsp <= 0) return 0;
@@ -276,8 +285,8 @@ int point_run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL>
     const long long n = WH * nsp;
     h->slots[0] += (uint64_t) n;
     const int own = wave_owns_pixels(h, nsp, n);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_camera<G, R, FL>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, pl, o->spp, o->spp_begin,
-                       SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own);
+    PSDR_BY_KIND(kind, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_camera<G, R, FL, LK>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, pl, o->spp,
+                                          o->spp_begin, SlotDiv(nsp), n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, own));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -285,24 +294,24 @@ int point_run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL>
 template <int FL>
 int point_render_c(psdr_scene_s *h, const psdr_render_opts *o, float *out_img, hipStream_t s) {
     const TangentView<0, FL> tv0{};
-    return point_run_camera<float, float, FL>(h, o, tv0, light_of(h, 0), out_img, nullptr, s);
+    return point_run_camera<float, float, FL>(h, o, tv0, h->point_kind, light_of(h, 0), out_img, nullptr, s);
 }
 
 // The two edge terms of forward mode for one light: primary edges and the shadow boundary, added into dimg (K planes, `plane` floats apart)
 template <int K, int FL>
-int point_edges_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const TangentView<K, FL> &tv, const PointLight &pl, float *dimg, long long plane, hipStream_t s) {
+int point_edges_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const TangentView<K, FL> &tv, int kind, const PointLight &pl, float *dimg, long long plane, hipStream_t s) {
     if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0) {
         EdgeLaunch e;
         if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_edge<K, FL>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppe, dimg, plane,
-                           h->d_counters, e.order);
+        PSDR_BY_KIND(kind, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_edge<K, FL, LK>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppe,
+                                              dimg, plane, h->d_counters, e.order));
         HIP_TRY(hipGetLastError());
     }
     if (o->sppse > 0 && o->sppse_end > o->sppse_begin && h->desc.num_sec_edges > 0) {
         EdgeLaunch e;
         if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_sedge<K, FL>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppse, dimg, plane,
-                           h->d_counters);
+        PSDR_BY_KIND(kind, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_sedge<K, FL, LK>), dim3(launch_blocks(h, e.n)), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, tv, pl, e.i0, e.n, 1.f / (float) o->sppse,
+                                              dimg, plane, h->d_counters));
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -316,9 +325,9 @@ int point_render_fwd_k(psdr_scene_s *h, const psdr_render_opts *o, const psdr_ta
     const PointLight pl = light_of(h, K);
     HIP_TRY(hipMemsetAsync(img, 0, sizeof(float) * WH * 3, s));
     HIP_TRY(hipMemsetAsync(dimg, 0, sizeof(float) * WH * 3 * K, s));
-    if (tangents_move_geometry(tangents, K) || light_moves(h, K)) { if (int rc = point_run_camera<Dual<K>, Dual<K>, FL>(h, o, tv, pl, img, dimg, s)) return rc; }
-    else { if (int rc = point_run_camera<float, Dual<K>, FL>(h, o, tv, pl, img, dimg, s)) return rc; }
-    return point_edges_fwd_k<K, FL>(h, o, tv, pl, dimg, WH * 3, s);
+    if (tangents_move_geometry(tangents, K) || light_moves(h, K)) { if (int rc = point_run_camera<Dual<K>, Dual<K>, FL>(h, o, tv, h->point_kind, pl, img, dimg, s)) return rc; }
+    else { if (int rc = point_run_camera<float, Dual<K>, FL>(h, o, tv, h->point_kind, pl, img, dimg, s)) return rc; }
+    return point_edges_fwd_k<K, FL>(h, o, tv, h->point_kind, pl, dimg, WH * 3, s);
 }
 template <int FL>
 int point_render_fwd(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, float *img, float *dimg, hipStream_t s) {
@@ -331,14 +340,14 @@ int point_render_fwd(psdr_scene_s *h, const psdr_render_opts *o, int K, const ps
 
 // The two edge terms of reverse mode for one light (gradient of its position: g_pos, +=, or null)
 template <int FL>
-int point_edges_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, DeviceSink<FL> &sink, const PointLight &pl, float *g_pos, hipStream_t s) {
+int point_edges_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, DeviceSink<FL> &sink, int kind, const PointLight &pl, float *g_pos, hipStream_t s) {
     if (o->sppe > 0 && o->sppe_end > o->sppe_begin && h->desc.num_prim_edges > 0 && grads->g_prim_edge) {
         EdgeLaunch e;
         if (int rc = begin_edge_term(h, o, 1, e, s)) return rc;
         PrimaryEdgeSink<FL> pe_sink;
         if (int rc = begin_pe_replicas(h, grads, e, pe_sink, s)) return rc;
-        hipLaunchKernelGGL(k_point_edge_rev<FL>, dim3(launch_blocks(h, e.n, big_launch_per_cu(h, e.n))), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, pe_sink, pl, e.i0, e.n, 1.f / (float) o->sppe,
-                           adj_img, h->d_counters, e.order);
+        PSDR_BY_KIND(kind, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_edge_rev<FL, LK>), dim3(launch_blocks(h, e.n, big_launch_per_cu(h, e.n))), dim3(kBlock), lds_bytes(e.cx, h), s, e.cx, pe_sink, pl, e.i0, e.n,
+                                              1.f / (float) o->sppe, adj_img, h->d_counters, e.order));
         HIP_TRY(hipGetLastError());
         if (int rc = end_pe_replicas(h, grads, pe_sink, s)) return rc;
     }
@@ -347,8 +356,9 @@ int point_edges_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *adj
         if (int rc = begin_edge_term(h, o, 2, e, s)) return rc;
         int dyn_bytes = 0;
         if (int rc = plan_rev_one_vertex(h, e.cx, sink.L, &dyn_bytes)) return rc;
-        if (int rc = allow_dynamic_lds(&k_point_sedge_rev<FL>, dyn_bytes)) return rc;
-        hipLaunchKernelGGL(k_point_sedge_rev<FL>, dim3(launch_blocks(h, e.n)), dim3(kBlock), dyn_bytes, s, e.cx, sink, pl, g_pos, e.i0, e.n, 1.f / (float) o->sppse, adj_img, h->d_counters);
+        PSDR_BY_KIND(kind, if (int rc = allow_dynamic_lds(&k_point_sedge_rev<FL, LK>, dyn_bytes)) return rc;
+                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_sedge_rev<FL, LK>), dim3(launch_blocks(h, e.n)), dim3(kBlock), dyn_bytes, s, e.cx, sink, pl, g_pos, e.i0, e.n, 1.f / (float) o->sppse, adj_img,
+                                        h->d_counters));
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -374,36 +384,37 @@ int point_render_rev(psdr_scene_s *h, const psdr_render_opts *o, const float *ad
         rev_layout_of_sink(h, sink.L, false);
         h->rev_layout[8] = kRevFused;
 #define PSDR_LAUNCH_POINT_REV(GEO)                                                                                                                                       \
-        do { if (int rc = allow_dynamic_lds(&k_point_camera_rev<FL, GEO>, dyn_bytes)) return rc;                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_camera_rev<FL, GEO>), dim3(launch_blocks(h, n)), dim3(kBlock), dyn_bytes, s, cx, sink, pl, g_pos, o->spp, o->spp_begin, SlotDiv(nsp), n,       \
-                           1.f / (float) o->spp, adj_img, out_img, h->d_counters); } while (0)
+        PSDR_BY_KIND(h->point_kind, if (int rc = allow_dynamic_lds(&k_point_camera_rev<FL, GEO, LK>, dyn_bytes)) return rc;                                               \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_camera_rev<FL, GEO, LK>), dim3(launch_blocks(h, n)), dim3(kBlock), dyn_bytes, s, cx, sink, pl, g_pos, o->spp, o->spp_begin, SlotDiv(nsp), n,   \
+                           1.f / (float) o->spp, adj_img, out_img, h->d_counters))
         if (geo) PSDR_LAUNCH_POINT_REV(true); else PSDR_LAUNCH_POINT_REV(false);
 #undef PSDR_LAUNCH_POINT_REV
         HIP_TRY(hipGetLastError());
     }
-    return point_edges_rev<FL>(h, o, adj_img, grads, sink, pl, g_pos, s);
+    return point_edges_rev<FL>(h, o, adj_img, grads, sink, h->point_kind, pl, g_pos, s);
 }
 
 // The edge terms for a light given by value, as the LightStageIntegrator (psdr_lightstage.hip) launches them once per light of its stack:
 // pos [3], d_pos [K][3] or null; dimg: the light's first derivative plane, `plane` floats to the next tangent's
 template <int FL>
-int point_edges_fwd_of(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, const float *pos, const float *d_pos, float *dimg, long long plane, hipStream_t s) {
+int point_edges_fwd_of(psdr_scene_s *h, const psdr_render_opts *o, int K, const psdr_tangents *tangents, int kind, const float *pos, const float *d_pos, float *dimg, long long plane, hipStream_t s) {
     PointLight pl{};
     for (int c = 0; c < 3; ++c) pl.p[c] = pos[c];
     for (int k = 0; k < K && d_pos; ++k) for (int c = 0; c < 3; ++c) pl.d[k][c] = d_pos[3 * k + c];
-    if (K == 1) { TangentView<1, FL> tv; tv.t[0] = tangents[0]; return point_edges_fwd_k<1, FL>(h, o, tv, pl, dimg, plane, s); }
+    if (K == 1) { TangentView<1, FL> tv; tv.t[0] = tangents[0]; return point_edges_fwd_k<1, FL>(h, o, tv, kind, pl, dimg, plane, s); }
     TangentView<3, FL> tv;
     for (int k = 0; k < 3; ++k) tv.t[k] = tangents[k];
-    return point_edges_fwd_k<3, FL>(h, o, tv, pl, dimg, plane, s);
+    return point_edges_fwd_k<3, FL>(h, o, tv, kind, pl, dimg, plane, s);
 }
 template <int FL>
-int point_edges_rev_of(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, const float *pos, float *g_pos, hipStream_t s) {
+int point_edges_rev_of(psdr_scene_s *h, const psdr_render_opts *o, const float *adj_img, const psdr_grads *grads, int kind, const float *pos, float *g_pos, hipStream_t s) {
     PointLight pl{};
     for (int c = 0; c < 3; ++c) pl.p[c] = pos[c];
     DeviceSink<FL> sink{};
     if (int rc = make_device_sink(h, grads, sink)) return rc;
-    return point_edges_rev<FL>(h, o, adj_img, grads, sink, pl, g_pos, s);
+    return point_edges_rev<FL>(h, o, adj_img, grads, sink, kind, pl, g_pos, s);
 }
+#undef PSDR_BY_KIND
 }  // namespace
 
 namespace psdr_host {

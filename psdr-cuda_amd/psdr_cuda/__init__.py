@@ -10,7 +10,7 @@ from .core import (Object, RenderOption, Bitmap1fD, Bitmap3fD, DiscreteDistribut
                    SampleRecordC, SampleRecordD, PositionSampleC, PositionSampleD)
 from .scene import (BSDF, Diffuse, DiffuseBSDF, RoughConductor, RoughConductorBSDF, MicrofacetBSDF, Emitter, AreaLight, EnvironmentMap,  # noqa: F401
                     Sensor, PerspectiveCamera, Mesh, Scene, PositionSample, BoundarySegSampleDirect)
-from .integrator import Integrator, FieldExtractionIntegrator, DirectIntegrator, PathTracer, CollocatedIntegrator, PointLightIntegrator, LightStageIntegrator  # noqa: F401
+from .integrator import Integrator, FieldExtractionIntegrator, DirectIntegrator, PathTracer, CollocatedIntegrator, PointLightIntegrator, DistantLightIntegrator, LightStageIntegrator  # noqa: F401
 from .largesteps import LargeSteps  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

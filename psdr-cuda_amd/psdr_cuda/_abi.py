@@ -27,6 +27,9 @@ SLOT_REFLECTANCE, SLOT_ALPHA_U, SLOT_ALPHA_V, SLOT_ETA, SLOT_K = range(5)
 CAM_SAMPLE_TO_CAMERA, CAM_TO_WORLD, CAM_WORLD_TO_SAMPLE, CAM_POS, CAM_DIR, CAM_INV_AREA = 0, 16, 32, 48, 51, 54
 INTEGRATOR_DIRECT, INTEGRATOR_PATH, INTEGRATOR_FIELD, INTEGRATOR_COLLOCATED, INTEGRATOR_POINT, INTEGRATOR_POINT_STACK = 0, 1, 2, 3, 4, 5
 POINT_LIGHTS_MAX = 256          # PSDR_POINT_LIGHTS_MAX
+LIGHT_POINT, LIGHT_DISTANT = 0, 1          # PSDR_LIGHT_*: the light models of kinds 4 and 5 (psdr_scene_set_light / psdr_scene_set_lights)
+# what the native render calls answer to a distant light under an environment map (psdr_hip.hip kDistantInEnv); the integrators raise it before the call
+DISTANT_IN_ENV = "a distant light cannot reach a scene inside an environment map's bounding mesh (env_emitter >= 0)"
 FLAG_FUSED, FLAG_WAVEFRONT, FLAG_LITERAL_FORMS, FLAG_KEEP_RECORDS, FLAG_PATH_SEDGES = 1, 2, 4, 8, 16
 MAX_PATH_SEDGE_DEPTH = 8          # csrc/psdr_path_sedge.h kMaxPathSedgeDepth
 FIELDS = {"silhouette": 0, "position": 1, "depth": 2, "geoNormal": 3, "shNormal": 4, "uv": 5}
@@ -95,7 +98,7 @@ TANGENT_FIELDS = ("tri_info", "texels", "emitter_rad", "cam_to_world", "sec_edge
 HIP_SYMBOLS = (
     "psdr_last_error", "psdr_version", "psdr_abi_struct_sizes", "psdr_scene_create", "psdr_scene_destroy", "psdr_scene_set_option", "psdr_scene_set_tables",
     "psdr_bvh_build", "psdr_bvh_stats", "psdr_scene_info", "psdr_trace", "psdr_render_c", "psdr_render_d_fwd", "psdr_render_d_rev",
-    "psdr_guide_build", "psdr_scene_set_point_light", "psdr_scene_set_point_lights", "psdr_scene_set_path_guide", "psdr_path_guide_build", "psdr_get_counters", "psdr_scene_rev_layout", "psdr_scene_seed_info", "psdr_scene_logd_info",
+    "psdr_guide_build", "psdr_scene_set_point_light", "psdr_scene_set_point_lights", "psdr_scene_set_light", "psdr_scene_set_lights", "psdr_scene_set_path_guide", "psdr_path_guide_build", "psdr_get_counters", "psdr_scene_rev_layout", "psdr_scene_seed_info", "psdr_scene_logd_info",
     "psdr_geo_world_vertices_fwd", "psdr_geo_world_vertices_rev", "psdr_geo_tri_rows_fwd", "psdr_geo_tri_rows_rev", "psdr_geo_sec_edges_fwd", "psdr_geo_sec_edges_rev", "psdr_geo_prim_edges_fwd", "psdr_geo_prim_edges_rev",
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
     "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
@@ -142,6 +145,8 @@ def load_hip():
     lib.psdr_guide_build.argtypes = [vp, C.POINTER(RenderOpts), C.POINTER(i32), i32, vp, vp]
     lib.psdr_scene_set_point_light.argtypes = [vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_float), vp]
     lib.psdr_scene_set_point_lights.argtypes = [vp, i32, C.POINTER(C.c_float), i32, C.POINTER(C.c_float), vp]
+    lib.psdr_scene_set_light.argtypes = [vp, i32, C.POINTER(C.c_float), i32, C.POINTER(C.c_float), vp]
+    lib.psdr_scene_set_lights.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_float), i32, C.POINTER(C.c_float), vp]
     lib.psdr_scene_set_path_guide.argtypes = [vp, C.POINTER(i32), vp, vp, C.c_float]
     lib.psdr_path_guide_build.argtypes = [vp, C.POINTER(RenderOpts), i32, C.POINTER(i32), i32, vp, vp]
     lib.psdr_get_counters.argtypes = [vp, C.POINTER(C.c_uint64)]

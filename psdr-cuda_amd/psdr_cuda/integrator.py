@@ -706,6 +706,7 @@ class PointLightIntegrator(CollocatedIntegrator):
     several integrators whose images add."""
     _type_name = "PointLightIntegrator"
     _kind = _abi.INTEGRATOR_POINT
+    _light_kind = _abi.LIGHT_POINT          # the model of m_position (DistantLightIntegrator: a direction)
 
     def __init__(self, position, intensity=1.0):
         super().__init__(intensity)
@@ -735,8 +736,12 @@ class PointLightIntegrator(CollocatedIntegrator):
         lib, keep = super()._prepare(scene, tb, guide)
         psdr_assert(self._light_state is not None, "PointLightIntegrator: no light in scope")
         pos, d_pos, g_pos = self._light_state
-        _abi.check(lib, lib.psdr_scene_set_point_light(scene._native, (C.c_float * 3)(*pos), 0 if d_pos is None else 1,
-                                                       None if d_pos is None else (C.c_float * 3)(*d_pos), None if g_pos is None else g_pos.data_ptr()))
+        args = ((C.c_float * 3)(*pos), 0 if d_pos is None else 1, None if d_pos is None else (C.c_float * 3)(*d_pos), None if g_pos is None else g_pos.data_ptr())
+        if self._light_kind == _abi.LIGHT_POINT:
+            _abi.check(lib, lib.psdr_scene_set_point_light(scene._native, *args))
+        else:
+            psdr_assert(not (tb.get("env_emitter", -1) >= 0), _abi.DISTANT_IN_ENV)
+            _abi.check(lib, lib.psdr_scene_set_light(scene._native, self._light_kind, *args))
         if g_pos is not None:
             keep.append(g_pos)
         return lib, keep
@@ -770,6 +775,43 @@ class PointLightIntegrator(CollocatedIntegrator):
             torch.cuda.synchronize()
             self.log("Rendered in %g seconds." % (time.perf_counter() - t0))
         return img
+
+
+class DistantLightIntegrator(PointLightIntegrator):
+    """A distant (directional) light: a direction and an irradiance, the light model of calibrated and uncalibrated photometric stereo, or the sun.  NOT in
+    the reference snapshot: build-defined.  direction points from the scene TOWARDS the light and need not be unit length; with u = direction / |direction|
+
+        Li = irradiance * f(its; wi = its.wi, wo = to_local(u)) * V(its.p, u)          (0 on a miss)
+
+    V the visibility along u to infinity; no 1 / r^2: irradiance is what a surface that faces the light receives, so a PointLightIntegrator at c + R u with
+    intensity irradiance * R^2 tends to this image as R grows.  Everything else is the PointLightIntegrator's: renderC / renderD, the three gradient terms
+    (the shadow boundary under parallel projection, csrc/psdr_pointlight.h), enoki.forward and enoki.backward, shards.
+
+    direction: three floats or a Vector3fD, kept as the differentiable attribute m_direction -- its gradient is that of the vector as passed: tangential,
+    and 1 / |direction| in size; irradiance: as CollocatedIntegrator's intensity, kept as m_intensity.  A scene inside an environment map's bounding mesh
+    cannot be reached by a distant light: rendering it raises."""
+    _type_name = "DistantLightIntegrator"
+    _light_kind = _abi.LIGHT_DISTANT
+
+    def __init__(self, direction, irradiance=1.0):
+        if isinstance(direction, Vector3fD):
+            psdr_assert(tuple(direction.t.shape) == (1, 3), "direction: one vector expected")
+            v = [float(x) for x in direction.t.detach().reshape(-1).cpu()]
+        else:
+            v = [float(x) for x in np.asarray(direction, dtype=np.float64).reshape(-1)]
+            psdr_assert(len(v) == 3, "direction: three finite floats expected")
+        psdr_assert(all(np.isfinite(v)), "direction: three finite floats expected")
+        psdr_assert(any(x != 0.0 for x in np.asarray(v, dtype=np.float32)), "direction: a vector that is not all zero expected")
+        super().__init__(direction if isinstance(direction, Vector3fD) else v, irradiance)
+
+    # the PointLightIntegrator reads m_position wherever it needs the light's vector: here that vector is m_direction
+    @property
+    def m_position(self):
+        return self.m_direction
+
+    @m_position.setter
+    def m_position(self, value):
+        self.m_direction = value
 
 
 class _StackRenderFn(torch.autograd.Function):
@@ -854,11 +896,15 @@ class LightStageIntegrator(PointLightIntegrator):
     positions: an [L, 3] array (1 <= L <= 256) or a Vector3fD of L rows, kept as the differentiable attribute m_positions; intensities: a float, one RGB
     triple or [L, 3] (or a Vector3fD of L rows), kept as m_intensities.  combine=False: renderC / renderD return L*H*W rows, light-major, plane l scaled
     by intensity l.  combine=True: they return the one image sum_l intensity_l * unit_l (H*W rows), formed in torch from the stack.  The tables, the
-    intensities and the positions take part in enoki.forward and enoki.backward."""
+    intensities and the positions take part in enoki.forward and enoki.backward.
+
+    distant: None, or a sequence of L booleans (not differentiable).  A flagged row of m_positions is a DIRECTION towards a distant light
+    (DistantLightIntegrator's model, its intensity an irradiance; the row's gradient is tangential and 1 / |row| in size); a stack may mix the two kinds
+    in any order.  None is a stack of point lights."""
     _type_name = "LightStageIntegrator"
     _kind = _abi.INTEGRATOR_POINT_STACK
 
-    def __init__(self, positions, intensities=1.0, combine=False):
+    def __init__(self, positions, intensities=1.0, combine=False, distant=None):
         Integrator.__init__(self)
         if isinstance(positions, Vector3fD):
             psdr_assert(positions.t.dim() == 2 and positions.t.shape[1] == 3, "positions: [L, 3] expected")
@@ -879,6 +925,16 @@ class LightStageIntegrator(PointLightIntegrator):
             self.m_intensities = Vector3fD(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)))
         self.combine = bool(combine)
         self._light_state = None
+        self.distant = None
+        if distant is not None:
+            flags = [bool(x) for x in distant]
+            psdr_assert(len(flags) == L, "distant: %d flags expected, one per light" % L)
+            rows = self.m_positions.t.detach().reshape(-1, 3).cpu().numpy()
+            for l in range(L):
+                if flags[l]:
+                    psdr_assert(np.isfinite(rows[l]).all(), "positions: an [L, 3] array of finite floats expected")
+                    psdr_assert((rows[l] != 0).any(), "positions: the direction of distant light %d is all zero" % l)
+            self.distant = flags
 
     def _lights(self, pos, d_pos=None, g_pos=None):
         """the lights every native call inside the block renders with (positions [L][3], their tangents in forward mode, their device gradient in reverse mode)"""
@@ -894,8 +950,13 @@ class LightStageIntegrator(PointLightIntegrator):
         L = len(pos)
         flat = [x for row in pos for x in row]
         dflat = None if d_pos is None else [x for row in d_pos for x in row]
-        _abi.check(lib, lib.psdr_scene_set_point_lights(scene._native, L, (C.c_float * (3 * L))(*flat), 0 if d_pos is None else 1,
-                                                        None if d_pos is None else (C.c_float * (3 * L))(*dflat), None if g_pos is None else g_pos.data_ptr()))
+        args = ((C.c_float * (3 * L))(*flat), 0 if d_pos is None else 1, None if d_pos is None else (C.c_float * (3 * L))(*dflat), None if g_pos is None else g_pos.data_ptr())
+        if self.distant is None:
+            _abi.check(lib, lib.psdr_scene_set_point_lights(scene._native, L, *args))
+        else:
+            psdr_assert(not (any(self.distant) and tb.get("env_emitter", -1) >= 0), _abi.DISTANT_IN_ENV)
+            kinds = (C.c_int32 * L)(*[_abi.LIGHT_DISTANT if f else _abi.LIGHT_POINT for f in self.distant])
+            _abi.check(lib, lib.psdr_scene_set_lights(scene._native, L, kinds, *args))
         if g_pos is not None:
             keep.append(g_pos)
         return lib, keep
