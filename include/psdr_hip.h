@@ -315,6 +315,9 @@ int psdr_scene_destroy(psdr_scene_t h);
    logd_park (1 default: forward-mode PathTracer launches with ONE tangent set on albedo texels, on a plain diffuse scene without a tree, run the lean twin of the
    log-derivative kernel, which keeps a path's idle state in per-lane LDS columns instead of scratch memory -- where staged scene + columns fit six workgroups per CU
    and a forced lds_budget; 0: always the kernel without columns; same results either way);
+   path_lean (1 default: fused PathTracer launches -- renderC, and forward mode with ONE tangent set on albedo texels -- on a plain diffuse scene without a tree run
+   the lean twins where every wave of the launch sits on one pixel (64 samples per pixel in the call) and every primitive is an axis-aligned rectangle: material
+   looked up once per vertex, film work on the scalar unit, slab-form ray tests only; 0: exactly the launches of before the twins; same results either way);
    trace_wg2 (dense trace kernel as two workgroups per CU: -1 by forest and launch size, 0 never, n > 0 always with stack columns of n entries);
    chunk_log2 (slots per chunk of the chunked launches, 0 = default); blocks_per_cu, camera_blocks, lds_budget, sink_rep, bvh_maxleaf (integers,
    0 = default where that makes sense); bvh_tcost (float).  Unknown names fail.  Options that change the tree take effect at the next psdr_bvh_build. */
@@ -550,6 +553,11 @@ int psdr_scene_seed_info(psdr_scene_t h, int64_t out[4]);
    twin ran, [2] those of the lean twin that loaded their seeds from the seed table, [3] dynamic LDS bytes per workgroup of the last lean launch (staged
    scene + parking columns; 0: none yet) }. */
 int psdr_scene_logd_info(psdr_scene_t h, int64_t out[4]);
+
+/* Fused PathTracer camera launches of the handle on flag set 8, plain diffuse without a tree (option path_lean; diagnostics): out = { [0] renderC launches the lean
+   twin ran, [1] K = 1 log-derivative launches the lean twin ran (counted by psdr_scene_logd_info as lean launches too), [2] renderC launches and [3] K = 1
+   log-derivative launches the selection rule left to the other kernels }. */
+int psdr_scene_path_lean_info(psdr_scene_t h, int64_t out[4]);
 
 /* Counters of the last render call on this handle (host values):
    [0] rays traced, [1] camera slots, [2] primary-edge slots, [3] secondary-edge slots. */

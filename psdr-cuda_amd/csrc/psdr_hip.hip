@@ -881,6 +881,7 @@ int psdr_scene_set_option(psdr_scene_t h, const char *name, double value) {
     else if (n == "logd") h->opt.logd = iv;                              // 0: PathTracer forward mode never runs the log-derivative kernel
     else if (n == "seed_cache") h->opt.seed_cache = iv;                  // 0: no seed table -- every camera kernel seeds its PCG32 streams itself
     else if (n == "logd_park") h->opt.logd_park = iv;                    // 0: K = 1 log-derivative launches on a scene without a tree run k_camera_logd, not its lean twin (psdr_logd_lean.hip)
+    else if (n == "path_lean") h->opt.path_lean = iv;                    // 0: no lean PathTracer twins (psdr_path_lean.h) -- exactly the launches of before them
     else if (n == "seed_cache_log2") h->opt.seed_cache_log2 = std::max(0, std::min(40, iv));   // log2 of the largest launch (in slots) the seed table serves (default 25: 512 MB)
     else if (n == "keep_records") h->opt.keep_records = iv;              // 0: psdr_render_c ignores PSDR_FLAG_KEEP_RECORDS
     else if (n == "rev_sorted") h->opt.rev_sorted = iv;                  // 0: the reverse camera kernels scatter every row adjoint on the spot (no deferred, sorted adds)
@@ -1441,6 +1442,11 @@ int psdr_scene_rev_layout(psdr_scene_t h, int32_t out[16]) {
 int psdr_scene_logd_info(psdr_scene_t h, int64_t out[4]) {
     if (!h || !out) return fail("psdr_scene_logd_info: null argument");
     out[0] = h->logd_launches; out[1] = h->logd_lean_launches; out[2] = h->logd_lean_seeded; out[3] = (int64_t) h->logd_lean_lds + h->logd_lean_park;
+    return 0;
+}
+int psdr_scene_path_lean_info(psdr_scene_t h, int64_t out[4]) {
+    if (!h || !out) return fail("psdr_scene_path_lean_info: null argument");
+    out[0] = h->path_lean_launches[0]; out[1] = h->path_lean_launches[1]; out[2] = h->path_lean_fallbacks[0]; out[3] = h->path_lean_fallbacks[1];
     return 0;
 }
 int psdr_scene_seed_info(psdr_scene_t h, int64_t out[4]) {

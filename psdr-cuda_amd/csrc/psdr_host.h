@@ -176,6 +176,7 @@ struct psdr_scene_options {
     int seed_cache = 1;                    // PathTracer renderC launches on a scene without a tree load their PCG32 seeds from the handle's seed table (psdr_kernels.h seed_table); 0: every kernel seeds its streams itself
     int seed_cache_log2 = 25;              // log2 of the largest launch the seed table serves, in slots (16 bytes each: 512 MB)
     int logd_park = 1;                     // K = 1 log-derivative launches on a plain diffuse scene without a tree run the lean twin, whose idle path state sits in LDS columns (psdr_logd_lean.h); 0: k_camera_logd
+    int path_lean = 1;                     // fused PathTracer launches on a plain diffuse scene without a tree whose waves each sit on one pixel and whose primitives are all slab-form rectangles run the lean twins (psdr_path_lean.h, psdr_plan.h path_lean_form); 0: exactly the launches of before the twins
     int bvh_maxleaf = 4;                   // host SAH builder: leaf size limit (1..8)
     float bvh_tcost = 2.0f;                //                   cost of a node visit in triangle tests
 };
@@ -285,6 +286,7 @@ struct psdr_scene_s {
     long long seed_fills = 0, seed_launches = 0;      // psdr_scene_seed_info
     long long logd_launches = 0, logd_lean_launches = 0, logd_lean_seeded = 0;      // psdr_scene_logd_info
     int logd_lean_lds = 0, logd_lean_park = 0;        //   dynamic LDS of the last lean launch: staged scene, parking columns (bytes)
+    long long path_lean_launches[2] = {0, 0}, path_lean_fallbacks[2] = {0, 0};      // psdr_scene_path_lean_info: launches the twins ran / launches path_lean_form left to the other kernels, [0] renderC (K = 0), [1] log-derivative K = 1
     // wavefront PathTracer: path-state streams + stream counters
     void *d_ws = nullptr;
     size_t ws_bytes = 0;
@@ -437,6 +439,9 @@ const LightStageOps *light_stage_ops_10();
 // sets *ran, or leaves *ran false -- option logd_park 0, or the parking columns do not fit six workgroups per CU (or a forced lds_budget) -- and
 // run_camera launches k_camera_logd.  cx: the launch context of run_camera (off_park is set on a copy).
 int logd_lean_launch_8(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCtx &cx, const psdr::TangentView<1, psdr::kSceneTiny> &tv, float *img, float *dimg, hipStream_t s, bool *ran);
+// The lean renderC twin of flag set 8 (psdr_path_lean.hip): launches k_camera_path_lean where path_lean_form chooses it and sets *ran, or leaves *ran false and
+// run_camera launches k_camera_seeded / k_camera.
+int path_lean_launch_8(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCtx &cx, const psdr::TangentView<0, psdr::kSceneTiny> &tv, float *img, float *dimg, hipStream_t s, bool *ran);
 const VariantOps *variant_ops_0();
 const VariantOps *variant_ops_1();
 const VariantOps *variant_ops_2();

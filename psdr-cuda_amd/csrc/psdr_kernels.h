@@ -1892,6 +1892,14 @@ int run_camera(psdr_scene_s *h, const psdr_render_opts *o, const TV<R, FL> &tv, 
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_camera<G, R, INTEG, FL, NOTREE>), dim3(launch_blocks(h, n, camera_blocks_per_cu(h, n))), dim3(kBlock), lds_bytes(cx, h), s, cx, tv, o->spp, \
                        o->spp_begin, nsp, n, 1.f / (float) o->spp, img, dimg, WH * 3, h->d_counters, 0ll, ProbeView{nullptr, nullptr}, own)
 #define PSDR_LAUNCH_CAMERA(INTEG) PSDR_LAUNCH_CAMERA_T(INTEG, ((FL & kSceneTiny) != 0))
+    // renderC of the PathTracer on a plain diffuse scene without a tree: the lean twin where the launch has its form (psdr_plan.h path_lean_form, psdr_path_lean.hip)
+    if constexpr (FL == kSceneTiny && seeded_render_c<G, R, FL>()) {
+        if (o->integrator == PSDR_INTEGRATOR_PATH) {
+            bool lean = false;
+            if (int rc = path_lean_launch_8(h, o, cx, tv, img, dimg, s, &lean)) return rc;
+            if (lean) { HIP_TRY(hipGetLastError()); return 0; }
+        }
+    }
     // renderC of the PathTracer on a scene without a tree: the seeded twin where the handle's seed table serves the launch
     if constexpr (seeded_render_c<G, R, FL>()) {
         if (o->integrator == PSDR_INTEGRATOR_PATH) {

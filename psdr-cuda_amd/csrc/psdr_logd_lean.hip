@@ -1,10 +1,12 @@
 // psdr_logd_lean.hip -- the lean twin of the log-derivative camera kernel (psdr_logd_lean.h) for flag set 8 (plain diffuse, no tree) and its launch.
 // A translation unit of its own: the twin's register allocation does not depend on, and does not disturb, the other kernels of the flag set
-// (tests/test_isa_guard.py pins those).
+// (tests/test_isa_guard.py pins those).  The K = 1 instances of the lean PathTracer twin (psdr_path_lean.h: k_camera_logd_path_lean<1, SEEDED>) live here too: the launch
+// below tries that twin's form first.
 #define PSDR_WIDE_TREE 0
 #define PSDR_LEAF_PAIR 0
 #include "psdr_kernels.h"
 #include "psdr_logd_lean.h"
+#include "psdr_path_lean.h"
 
 namespace {
 
@@ -78,6 +80,9 @@ namespace psdr_host {
 // the CU's 160 KiB, and within a forced lds_budget (tests).  The seeded form under the conditions of the seeded renderC kernel (seed_table).
 int logd_lean_launch_8(psdr_scene_s *h, const psdr_render_opts *o, const LaunchCtx &cx0, const psdr::TangentView<1, psdr::kSceneTiny> &tv, float *img, float *dimg, hipStream_t s, bool *ran) {
     *ran = false;
+    // the launch the headline makes (every wave on one pixel, slab-form rows only): the twin of psdr_path_lean.h
+    if (int rc = path_lean_launch<1>(h, o, cx0, tv, img, dimg, s, ran)) return rc;
+    if (*ran) return 0;
     if (h->opt.logd_park == 0) return 0;
     constexpr int kCuLds = 160 * 1024, park = ParkLayout<1>::cols * kBlock * 4;
     const int lds = (lds_bytes(cx0, h) + 15) / 16 * 16;

@@ -193,6 +193,45 @@ inline bool probe_direct(const psdr_scene_s *h, const psdr_render_opts *o, long 
 inline bool wave_owns_pixels(const psdr_scene_s *h, int nsp, long long chunk) {
     return h->opt.own_pixels != 0 && nsp <= 64 && 64 % nsp == 0 && chunk % nsp == 0;
 }
+// ---- the lean PathTracer twins of flag set 8 (psdr_path_lean.h): which kernel a fused PathTracer camera launch on a scene without a tree runs.
+// kPathLeanNone: the kernels of before the twins -- k_camera / k_camera_seeded (K = 0), k_camera_logd_lean or k_camera_logd (K >= 1, logd_lean_launch_8).
+// kPathLeanOwnSlab: k_camera_path_lean (K = 0) / k_camera_logd_path_lean<K>.  The twins exist in ONE form, "every wave on one pixel, every row a slab-form rectangle": a general form of them beside
+// the kernels that already serve every other launch would only add four kernels to the library.
+enum PathLeanForm { kPathLeanNone = 0, kPathLeanOwnSlab = 1 };
+// parking columns of the twin per K (psdr_path_lean.h LeanLayout<K>::cols; 0: the twin holds everything in registers).  K = 0 has none: without columns the
+// renderC twin takes 77 / 79 VGPRs and spills nothing (profiles/path_lean_ab.txt, the compile-only table); PSDR_PATH_LEAN_PARK_K0=1 builds it with columns (A/B)
+#ifndef PSDR_PATH_LEAN_PARK_K0
+#define PSDR_PATH_LEAN_PARK_K0 0
+#endif
+constexpr int path_lean_cols(int K) { return (K == 0 && !PSDR_PATH_LEAN_PARK_K0) ? 0 : 16 + 6 * K; }
+constexpr int kPathLeanWaves = 6;          // the twins' waves per SIMD = workgroups per CU that keep their LDS blocks side by side
+// what the rule reads: of the launch, of the scene, of the options
+struct PathLeanCase {
+    int flags, K, integrator, texels_only;          // flag set of the scene's kernels; tangent sets; PSDR_INTEGRATOR_*; K >= 1: every tangent set moves albedo texels only (the log-derivative launch)
+    int nsp; long long chunk;                       // samples per pixel of the launch; its slots (or the slots per chunk of a chunked one)
+    int n_tiny, aa_cnt, n_blas;                     // rows of kernel-argument primitives, slab-form slots per axis, trees
+    int lds_scene, lds_budget;                      // staged scene in bytes (16-byte aligned); forced budget (0: none)
+    int own_pixels, path_lean, logd_park;           // options
+};
+// every wave of the launch sits on ONE pixel and no wave is partial: wave_owns_pixels with exactly a wave's samples per pixel (fewer: a wave holds several
+// pixels; more: a pixel's samples sit in several waves and the launch adds with atomics)
+inline bool wave_is_pixel(int own_pixels, int nsp, long long chunk) { return own_pixels != 0 && nsp == 64 && chunk % nsp == 0; }
+// every kernel-argument primitive is a slab-form rectangle: the plane-form rows, which start at kAaSlots, are none
+inline bool slab_only(int n_tiny, int aa_cnt, int n_blas) { return n_blas == 0 && aa_cnt != 0 && n_tiny > 0 && n_tiny <= kAaSlots; }
+inline int path_lean_form(const PathLeanCase &c) {
+    if (c.path_lean == 0 || c.flags != kSceneTiny || c.integrator != PSDR_INTEGRATOR_PATH) return kPathLeanNone;
+    if (!(c.K == 0 || (c.K == 1 && c.texels_only != 0 && c.logd_park != 0))) return kPathLeanNone;          // K = 3 keeps k_camera_logd
+    if (!wave_is_pixel(c.own_pixels, c.nsp, c.chunk) || !slab_only(c.n_tiny, c.aa_cnt, c.n_blas)) return kPathLeanNone;
+    constexpr int kCuLds = 160 * 1024;
+    const int limit = c.lds_budget > 0 ? std::min(c.lds_budget, kCuLds / kPathLeanWaves) : kCuLds / kPathLeanWaves;
+    const int park = path_lean_cols(c.K) * kBlock * 4;
+    if (park > 0 && c.lds_scene + park > limit) return kPathLeanNone;
+    return kPathLeanOwnSlab;
+}
+inline int path_lean_form(const psdr_scene_s *h, int flags, int K, int integrator, bool texels_only, int nsp, long long chunk, int lds_scene) {
+    const PathLeanCase c{flags, K, integrator, texels_only ? 1 : 0, nsp, chunk, h->n_tiny, h->aa_cnt, h->n_blas, lds_scene, h->opt.lds_budget, h->opt.own_pixels, h->opt.path_lean, h->opt.logd_park};
+    return path_lean_form(c);
+}
 // The secondary-edge term as filter + survivor kernel (option sedge_split: 1 / 0 force, -1 from 2^18 slots); a survivor list holds 32-bit slots
 inline bool path_sedge_split(const psdr_scene_s *h, long long n) {
     const int split_env = h->opt.sedge_split;

@@ -98,7 +98,7 @@ TANGENT_FIELDS = ("tri_info", "texels", "emitter_rad", "cam_to_world", "sec_edge
 HIP_SYMBOLS = (
     "psdr_last_error", "psdr_version", "psdr_abi_struct_sizes", "psdr_scene_create", "psdr_scene_destroy", "psdr_scene_set_option", "psdr_scene_set_tables",
     "psdr_bvh_build", "psdr_bvh_stats", "psdr_scene_info", "psdr_trace", "psdr_render_c", "psdr_render_d_fwd", "psdr_render_d_rev",
-    "psdr_guide_build", "psdr_scene_set_point_light", "psdr_scene_set_point_lights", "psdr_scene_set_light", "psdr_scene_set_lights", "psdr_scene_set_path_guide", "psdr_path_guide_build", "psdr_get_counters", "psdr_scene_rev_layout", "psdr_scene_seed_info", "psdr_scene_logd_info",
+    "psdr_guide_build", "psdr_scene_set_point_light", "psdr_scene_set_point_lights", "psdr_scene_set_light", "psdr_scene_set_lights", "psdr_scene_set_path_guide", "psdr_path_guide_build", "psdr_get_counters", "psdr_scene_rev_layout", "psdr_scene_seed_info", "psdr_scene_logd_info", "psdr_scene_path_lean_info",
     "psdr_geo_world_vertices_fwd", "psdr_geo_world_vertices_rev", "psdr_geo_tri_rows_fwd", "psdr_geo_tri_rows_rev", "psdr_geo_sec_edges_fwd", "psdr_geo_sec_edges_rev", "psdr_geo_prim_edges_fwd", "psdr_geo_prim_edges_rev",
     "psdr_geo_compact_edges_fwd", "psdr_geo_compact_edges_rev", "psdr_geo_emitter_tables",
     "psdr_geo_world_vertices_jvp", "psdr_geo_tri_rows_jvp", "psdr_geo_sec_edges_jvp", "psdr_geo_prim_edges_jvp", "psdr_geo_compact_edges_jvp",
@@ -154,6 +154,7 @@ def load_hip():
     lib.psdr_scene_rev_layout.argtypes = [vp, C.POINTER(i32)]
     lib.psdr_scene_seed_info.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.psdr_scene_logd_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.psdr_scene_path_lean_info.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.psdr_geo_world_vertices_fwd.argtypes = [i32, vp, vp, vp, vp, vp]
     lib.psdr_geo_world_vertices_rev.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
     lib.psdr_geo_tri_rows_fwd.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
@@ -235,6 +236,15 @@ def logd_info(handle):
     out = (C.c_int64 * 4)()
     check(lib, lib.psdr_scene_logd_info(handle, out))
     return {"launches": int(out[0]), "lean": int(out[1]), "lean_seeded": int(out[2]), "lean_lds_bytes": int(out[3])}
+
+
+def path_lean_info(handle):
+    """psdr_scene_path_lean_info as a dict: the handle's fused PathTracer launches on a plain diffuse scene without a tree -- those the lean twins ran (option
+    path_lean; renderC, K = 1 log-derivative) and those the selection rule left to the other kernels."""
+    lib = load_hip()
+    out = (C.c_int64 * 4)()
+    check(lib, lib.psdr_scene_path_lean_info(handle, out))
+    return {"render_c": int(out[0]), "logd": int(out[1]), "render_c_fallback": int(out[2]), "logd_fallback": int(out[3])}
 
 
 def make_opts(integrator=INTEGRATOR_DIRECT, bsdf_samples=1, light_samples=1, max_depth=1, hide_emitters=False,

@@ -15,7 +15,7 @@ if [ -n "${ONLY:-}" ]; then cp $ROOT/psdr-cuda_amd/lib/obj/*.o $obj/; rm -f $obj
 for v in $SET; do if [ "$v" = "host" ]; then hipcc $FLAGS "$@" -c psdr_hip.hip -o $obj/host.o & fi; done
 SET=$(echo $SET | sed "s/host//")
 for v in $SET; do hipcc $FLAGS "$@" -DPSDR_VARIANT_FLAGS=$v -c psdr_variant.hip -o $obj/variant$v.o & done
-if [ -z "${ONLY:-}" ]; then hipcc $FLAGS "$@" -c psdr_hip.hip -o $obj/host.o & hipcc $FLAGS "$@" -c psdr_tables.hip -o $obj/tables.o & hipcc $FLAGS "$@" -c psdr_logd_lean.hip -o $obj/logd_lean.o & fi
+if [ -z "${ONLY:-}" ]; then hipcc $FLAGS "$@" -c psdr_hip.hip -o $obj/host.o & hipcc $FLAGS "$@" -c psdr_tables.hip -o $obj/tables.o & hipcc $FLAGS "$@" -c psdr_logd_lean.hip -o $obj/logd_lean.o & hipcc $FLAGS "$@" -c psdr_path_lean.hip -o $obj/path_lean.o & fi
 wait
 hipcc --offload-arch=gfx950 -shared -fPIC $obj/*.o -o $ROOT/variants/lib_$name.so
 echo built variants/lib_$name.so
